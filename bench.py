@@ -14,10 +14,17 @@ resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
 Workload = BASELINE.json configs[2] ("c3": 1M Gaussians, 1920x1080, SH degree 3, HDR linear radiance + learned CRF
 tone-map), the configuration the metric is quoted on; at N>1 each rank renders its own view of the same cloud
-(configs[4]).  Synthetic scene: SURVEY.md 8(d); seeds {0,1,2} are each timed the same way (W warm-up + K steps, fresh scene
-and rasterizers) and the headline `value` / `ms_per_step` is their MEDIAN (`seeds_ms_per_step` has all three).
+(configs[4]).  Synthetic scene: SURVEY.md 8(d).
 
-Extra objects on the line (all measured in this run unless marked `from_profiles`):
+A plain run does only what the headline needs: it builds the seed-0 scene, warms up W steps, times exactly K steps
+(`value` / `ms_per_step` are those K steps) and prints the line.  `--dump-outputs DIR` then also writes what the last
+timed step handed its caller (images, radii, every parameter gradient) as float32 .npy files under DIR (dump_outputs).
+
+`--full` runs everything else as well: seeds {0,1,2} are each timed the same way (W warm-up + K steps, fresh scene and
+rasterizers) and the headline `value` / `ms_per_step` is their MEDIAN (`seeds_ms_per_step` has all three); c3 also times
+c2 and c4 (`other_configs`), and the line carries `stages_ms`, `render_stats`, the roofline and the CPU baseline.
+
+Extra objects on a --full line (all measured in this run unless marked `from_profiles`):
   roofline      -- the dominant kernel (render_bwd_kernel): algorithmic bytes per launch (76*R' + 20*W*H) /
                    its average duration measured here with HIP events on the launch stream; peak = 8 TB/s HBM3E.
                    `fwd_bwd` repeats the figure for the per-tile alpha-blend forward+backward pair
@@ -141,7 +148,8 @@ def build_step(cfg, rank, world, dev, seed=0):
                 "views_overlap": GaussianRasterizer(rs, capacity=capacity, defer_sh_grad=True, gather_group=True)}
 
     # exchange = (what goes on the wire, all-reduce algorithm); chosen by measurement in main() when world > 1
-    state = {"rast": make_rasterizer(None), "out": None, "exchange": ("allreduce", "rccl")}
+    state = {"rast": make_rasterizer(None), "out": None, "exchange": ("allreduce", "rccl"),
+             "param_names": list(params) + (["exposure", "crf_table"] if hdr else [])}   # (names of plist, for --dump-outputs)
 
     def step():
         mode, algo = state["exchange"]
@@ -213,6 +221,37 @@ def derived_counts(out, W, H, n_poses):
     pad[:, :H, :W] = nc
     tmax = pad.reshape(n_poses, gy, 16, gx, 16).amax(dim=(2, 4))
     return int(st["num_rendered"]), int(tmax.sum()), int(nc.sum()), gx * gy * n_poses
+
+
+DUMP_ROWS = 16384             # --dump-outputs: rows written of every per-Gaussian array (a fixed seeded sample)
+DUMP_MAX_BYTES = 64 * 10**6
+
+
+def dump_outputs(out_dir, state, plist, P):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files -- `image` (LDR), `hdr_image`
+    (HDR configs), `radii` and `grad_<parameter>` of every parameter.  Images and per-frame tensors are written whole; an
+    array with one row per Gaussian only at the rows listed in `gaussian_rows.npy` (the same seeded sample every run), which
+    keeps the files under 64 MB at 1M Gaussians.  The scene is seeded too, so two builds run with the same arguments can be
+    compared file for file."""
+    import numpy as np
+    import torch
+    rows = np.sort(np.random.default_rng(0).choice(P, size=min(P, DUMP_ROWS), replace=False))
+    idx = torch.from_numpy(rows).to(state["out"][0].device)
+    arrays = dict(zip(("image", "radii", "hdr_image"), state["out"]))
+    arrays.update({f"grad_{n}": p.grad for n, p in zip(state["param_names"], plist) if p.grad is not None})
+    files = {"gaussian_rows": rows.astype(np.float64)}
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dim() and t.shape[0] == P:
+            t = t.index_select(0, idx)
+        files[name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"[bench] --dump-outputs: {total} bytes > {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
 
 
 def time_stage(fn, iters):
@@ -633,15 +672,20 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(c for c in CONFIGS if c != "c1"))
+    ap.add_argument("--full", action="store_true",
+                    help="also the median of seeds {0,1,2}, per-stage times, roofline, render stats, other_configs and the "
+                         "CPU baseline (the options below trim these); without it only seed 0's K steps are timed")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cpu-c2", action="store_true",
                     help="skip BASELINE config c2 in full on the CPU (BASELINE.md 3: 'config 2 if it completes in < 10 min'; "
-                         "it takes ~2.5 min on the 128 host cores of the MI355X box and is part of the default run)")
-    ap.add_argument("--cpu-c2", action="store_true", help="(kept for older command lines: c2 in full is the default now)")
-    ap.add_argument("--no-extras", action="store_true", help="profiling runs: one seed only, no CPU baseline")
-    ap.add_argument("--one-seed", action="store_true", help="time seed 0 only (the headline is then NOT the median of seeds)")
+                         "it takes ~2.5 min on the 128 host cores of the MI355X box and is part of a --full run)")
+    ap.add_argument("--cpu-c2", action="store_true", help="(kept for older command lines: --full runs c2 in full)")
+    ap.add_argument("--no-extras", action="store_true", help="profiling runs with --full: one seed only, no CPU baseline")
+    ap.add_argument("--one-seed", action="store_true", help="with --full: time seed 0 only (the headline is then NOT the median of seeds)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default c3 runs also time BASELINE configs c2 and c4 once each (other_configs, ~10 s): skip that")
+                    help="--full c3 runs also time BASELINE configs c2 and c4 once each (other_configs, ~10 s): skip that")
     ap.add_argument("--kernel-iters", type=int, default=10)
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the whole step as one HIP graph (single GPU).  auto = only where the host can pace the "
@@ -676,9 +720,10 @@ def main():
 
     exchange = {"info": None, "choice": None}   # the gradient exchange is chosen once (first seed) and reused
 
-    def bench_config(cfg_name, seeds, steps, warmup):
-        """Time one BASELINE config (median over `seeds`, each by the same procedure) and, on rank 0, its per-stage /
-        roofline legs on the median seed's scene.  Returns (line, scene, cfg)."""
+    def bench_config(cfg_name, seeds, steps, warmup, dump_dir=None):
+        """Time one BASELINE config (median over `seeds`, each by the same procedure) and, with --full on rank 0, its
+        per-stage / roofline legs on the median seed's scene; `dump_dir`: dump_outputs of the first seed's last timed step.
+        Returns (line, scene, cfg)."""
         cfg = CONFIGS[cfg_name]
         P, W, H, deg, hdr, n_poses = cfg
 
@@ -780,6 +825,8 @@ def main():
             torch.cuda.empty_cache()
             ctx, ms = time_seed(seed)
             per_seed[seed] = {"ms_per_step": ms, "R": ctx["counts"][0], "R_prime": ctx["counts"][1]}
+            if dump_dir and seed == seeds[0] and rank == 0:
+                dump_outputs(dump_dir, ctx["state"], ctx["plist"], P)
         order = sorted(seeds, key=lambda s_: per_seed[s_]["ms_per_step"])
         med_seed = order[len(order) // 2]
         ms_per_step = per_seed[med_seed]["ms_per_step"]
@@ -816,7 +863,7 @@ def main():
         if allreduce_info is not None:
             line["config"]["gradient_exchange"] = allreduce_info
 
-        if rank == 0:
+        if rank == 0 and args.full:
             from casualhdrsplat_amd import _lib as L
             from casualhdrsplat_amd.rasterizer import render_stats, replay_backward, replay_forward
             # a fresh forward whose autograd graph is kept (never .backward()-ed) so its stages can be replayed
@@ -951,12 +998,12 @@ def main():
             line["render_stats"] = stats
         return line, sc, cfg
 
-    seeds_main = [0] if (args.one_seed or args.no_extras) else [0, 1, 2]
-    line, sc, cfg = bench_config(args.config, seeds_main, args.steps, args.warmup)
+    seeds_main = [0, 1, 2] if args.full and not (args.one_seed or args.no_extras) else [0]
+    line, sc, cfg = bench_config(args.config, seeds_main, args.steps, args.warmup, dump_dir=args.dump_outputs)
     if rank == 0:
-        # BASELINE configs[1] and configs[3] on the driver's record too: after the c3 legs the default
+        # BASELINE configs[1] and configs[3] on the driver's record too: after the c3 legs a --full
         # run times c2 and c4 once each -- seed 0, the same time_seed procedure -- and prints their step, stages and roofline
-        if world == 1 and args.config == "c3" and not (args.no_extras or args.one_seed or args.no_other_configs):
+        if world == 1 and args.config == "c3" and args.full and not (args.no_extras or args.one_seed or args.no_other_configs):
             other = {}
             for name, k_steps in (("c2", max(args.steps, 50)), ("c4", max(5, min(args.steps, 12)))):
                 torch.cuda.empty_cache()
@@ -972,7 +1019,7 @@ def main():
                                "per_kernel": o["roofline"]["per_kernel"]}
             line["other_configs"] = other
             torch.cuda.empty_cache()
-        if world == 1 and not (args.no_cpu_baseline or args.no_extras):
+        if world == 1 and args.full and not (args.no_cpu_baseline or args.no_extras):
             line["cpu_baseline"] = cpu_baseline(sc, cfg, with_c2=not args.no_cpu_c2)
         print(json.dumps(line), flush=True)
     if world > 1:

@@ -39,16 +39,16 @@ if [ "$what" = pmc ] || [ "$what" = all ]; then
 fi
 if [ "$what" = bench ] || [ "$what" = all ]; then
   if [ "$CFG" = c3 ]; then
-  python3 $ROOT/bench.py --steps 50 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err
-  python3 $ROOT/bench.py --config c4 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.err
-  python3 $ROOT/bench.py --config c2 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err
+  python3 $ROOT/bench.py --full --steps 50 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err
+  python3 $ROOT/bench.py --full --config c4 --steps 20 --warmup 3 --no-cpu-baseline > $O/bench_c4.json 2> $O/bench_c4.err
+  python3 $ROOT/bench.py --full --config c2 --steps 50 --warmup 5 --no-cpu-baseline > $O/bench_c2.json 2> $O/bench_c2.err
   fi
   # per-kernel totals of the bench command at this config (the driver's command at c3)
   extra=""; [ "$CFG" = c3 ] || extra="--config $CFG"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $ROOT/bench.py $extra --steps 10 --warmup 3 --no-cpu-baseline --no-extras --graph off > $O/stats.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $ROOT/bench.py --full $extra --steps 10 --warmup 3 --no-cpu-baseline --no-extras --graph off > $O/stats.log 2>&1
   if [ "$CFG" = c3 ]; then
   # plumbing check of the bare multi-GPU invocation on a one-GPU box: bench.py starts its own two ranks (gloo, shared GPU)
-  HS_BENCH_BACKEND=gloo timeout 900 python3 $ROOT/bench.py --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo_one_gpu.json 2> $O/bench_2rank.err
+  HS_BENCH_BACKEND=gloo timeout 900 python3 $ROOT/bench.py --full --gpus 2 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo_one_gpu.json 2> $O/bench_2rank.err
   python3 $ROOT/scripts/timeline.py > $O/timeline.txt 2>&1
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O2 $ROOT/scripts/ubench/valu_rate.hip -o /tmp/valu_rate && /tmp/valu_rate > $O/valu_rate.txt 2>&1 || true
   fi

@@ -132,6 +132,40 @@ def test_bench_self_launches_ranks_and_forwards_their_exit_code():
     assert not r.stdout.strip().startswith("{")
 
 
+def test_bench_dump_outputs_at_c3_size(tmp_path):
+    """`bench.py --dump-outputs DIR` at the size of c3 (1M Gaussians, SH degree 3, 1080p, HDR): the step's images whole,
+    every per-Gaussian array at the same seeded rows on every run, float32 / float64 only, under 64 MB in all."""
+    import numpy as np
+    import bench
+    P, W, H, M = 1_000_000, 1920, 1080, 16
+    g = torch.Generator().manual_seed(3)
+    shapes = {"means3D": (P, 3), "means2D": (P, 3), "opacities": (P, 1), "shs": (P, M, 3), "scales": (P, 3),
+              "rotations": (P, 4), "exposure": (1,), "crf_table": (3, 256)}
+    plist = []
+    for shp in shapes.values():
+        p = torch.zeros(shp, requires_grad=True)
+        p.grad = torch.randn(shp, generator=g)
+        plist.append(p)
+    out = (torch.rand(3, H, W, generator=g), torch.randint(0, 50, (P,), generator=g, dtype=torch.int32),
+           torch.rand(3, H, W, generator=g))
+    state = {"out": out, "param_names": list(shapes)}
+    total = bench.dump_outputs(str(tmp_path / "a"), state, plist, P)
+    assert total <= 64 * 10**6
+    assert bench.dump_outputs(str(tmp_path / "b"), state, plist, P) == total
+    files = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(files) == {"gaussian_rows", "image", "radii", "hdr_image"} | {f"grad_{n}" for n in shapes}
+    assert sum(a.nbytes for a in files.values()) == total
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    rows = files["gaussian_rows"].astype(np.int64)
+    assert len(rows) == bench.DUMP_ROWS and np.all(np.diff(rows) > 0) and rows[-1] < P
+    assert np.array_equal(np.load(tmp_path / "b" / "gaussian_rows.npy"), files["gaussian_rows"])
+    assert np.array_equal(files["image"], out[0].numpy()) and np.array_equal(files["hdr_image"], out[2].numpy())
+    assert np.array_equal(files["radii"], out[1].numpy()[rows].astype(np.float32))
+    for n, p in zip(shapes, plist):
+        want = p.grad.numpy()[rows] if p.shape[0] == P else p.grad.numpy()
+        assert np.array_equal(files[f"grad_{n}"], want), n
+
+
 def test_bench_offline_counters_are_tied_to_the_kernel_source(tmp_path, monkeypatch):
     """`roofline.traffic` may only carry the committed PMC figure while render.hip is the file the counters were
     collected on (hash recorded by scripts/fold_profiles.py); the committed profile must be current."""
