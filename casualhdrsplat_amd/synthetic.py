@@ -199,3 +199,76 @@ def blur_poses(W: int, H: int, n: int = 8, step: float = 0.01) -> list[Camera]:
         # camera centre at (k*step,0,0): x_view = x_world - centre
         cams.append(make_camera(W, H, None, torch.tensor([-k * step, 0.0, 0.0])))
     return cams
+
+
+def _retarget(sc: Scene, idx: torch.Tensor, px, py, z, sigma_px):
+    """Moves Gaussians `idx` (float64 draws) to screen position (px, py) at view depth z with footprint sigma_px (pixels),
+    in the scene's default camera (identity rotation, the cloud's frame)."""
+    cam = sc.camera
+    fx = cam.W / (2 * cam.tanfovx)
+    ndc_x, ndc_y = (2 * px + 1) / cam.W - 1, (2 * py + 1) / cam.H - 1
+    sc.means3D[idx] = torch.stack([ndc_x * cam.tanfovx * z, ndc_y * cam.tanfovy * z, z], 1).float()
+    ratio = sc.scales[idx] / sc.scales[idx].mean(dim=1, keepdim=True)
+    sc.scales[idx] = ((sigma_px * z / fx)[:, None] * ratio.double()).float()
+
+
+def extreme_scene(name: str, seed: int = 0) -> Scene:
+    """Geometry where a kernel's long per-instance runs and edge paths live (tests: test_extreme_geometry_vs_oracle),
+    on the default camera of make_scene:
+      floaters      1920 x 1080, 50k Gaussians; 1 % floaters of sigma 100-400 px and opacity 0.05-0.3, five of sigma
+                    1500-3000 px that cover every tile (runs of 8160 tile records per instance)
+      near_plane    960 x 540; 3 % of the cloud at view z 0.2-0.3 (the cull distance is 0.2) with scales x 3
+      off_screen    960 x 540; 1 % of centres 2-5 frame widths outside the frame, footprints reaching into it
+      opaque_stack  960 x 540; six layers of opacity 0.99 discs at spread depths: T ends below 1e-4 at varied depths"""
+    g = torch.Generator().manual_seed(7_000_001 + seed)
+
+    def U(n, lo, hi):
+        return lo + (hi - lo) * torch.rand(n, generator=g, dtype=torch.float64)
+
+    def pick(P, n):
+        return torch.randperm(P, generator=g)[:n]
+
+    if name == "floaters":
+        W, H, P = 1920, 1080, 50_000
+        sc = make_scene(P, W, H, 1, seed=seed, hdr=True)
+        idx = pick(P, P // 100)
+        n = idx.numel()
+        _retarget(sc, idx, U(n, 0, W), U(n, 0, H), U(n, 2.0, 10.0), U(n, 100.0, 400.0))
+        sc.opacities[idx] = U(n, 0.05, 0.3).float()[:, None]
+        big = idx[:5]
+        _retarget(sc, big, U(5, 0.3 * W, 0.7 * W), U(5, 0.3 * H, 0.7 * H), U(5, 4.0, 9.0), U(5, 1500.0, 3000.0))
+        sc.opacities[big] = U(5, 0.05, 0.15).float()[:, None]
+        return sc
+    W, H = 960, 540
+    if name == "near_plane":
+        P = 15_000
+        sc = make_scene(P, W, H, 2, seed=seed)
+        idx = pick(P, P * 3 // 100)
+        z_old = sc.means3D[idx, 2].double()
+        z_new = U(idx.numel(), 0.2, 0.3)
+        sc.means3D[idx] = (sc.means3D[idx].double() * (z_new / z_old)[:, None]).float()
+        sc.scales[idx] *= 3.0
+    elif name == "off_screen":
+        P = 15_000
+        sc = make_scene(P, W, H, 2, seed=seed)
+        idx = pick(P, P // 100)
+        n = idx.numel()
+        side = torch.where(torch.rand(n, generator=g) < 0.5, -1.0, 1.0).to(torch.float64)
+        horiz = torch.rand(n, generator=g) < 0.5
+        dist = U(n, 2.0, 5.0)
+        px = torch.where(horiz, W / 2 + side * dist * W, U(n, 0, W))
+        py = torch.where(horiz, U(n, 0, H), H / 2 + side * dist * H)
+        reach = torch.where(horiz, (dist - 0.5) * W, (dist - 0.5) * H)          # centre to the near frame edge
+        _retarget(sc, idx, px, py, U(n, 2.0, 10.0), reach * U(n, 0.4, 0.6))      # 3 sigma: 1.2-1.8 x that distance
+        sc.opacities[idx] = U(n, 0.02, 0.3).float()[:, None]
+    elif name == "opaque_stack":
+        P = 15_000
+        sc = make_scene(P, W, H, 2, seed=seed)
+        idx = pick(P, 6 * 400)
+        n = idx.numel()
+        layer = torch.arange(n, dtype=torch.float64) % 6
+        _retarget(sc, idx, U(n, 0, W), U(n, 0, H), 2.0 + 1.3 * layer + U(n, 0.0, 0.5), U(n, 8.0, 40.0))
+        sc.opacities[idx] = 0.99
+    else:
+        raise ValueError(name)
+    return sc

@@ -336,6 +336,8 @@ def assert_grads_close(got: dict, ref: dict, keys=GRAD_KEYS, frac_tol=None, max_
                 k = int(d2.argmax())
                 n2 = (rr.astype(np.float64) ** 2).reshape(rr.shape[0], -1).sum(axis=1)
                 if k == int(n2.argmax()) and d2[k] <= (3e-4 ** 2) * n2[k]:
+                    if os.environ.get("HS_PARITY_REPORT"):
+                        print("L2_EXEMPTION", what, gk + tag, os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0], flush=True)
                     d2 = np.delete(d2, k)
             l2 = float(np.sqrt(d2.sum()) / max(np.linalg.norm(r.astype(np.float64)), 1e-30))
             report[gk + tag] = (mx, frac, l2)
@@ -496,14 +498,18 @@ def guarded_scene(O, P, W, H, deg, seed=0, hdr=False, cams_fn=None, tries=2000, 
 C_BOUND = 8.0
 
 
-def assert_grads_bounded(got: dict, ref: dict, keys=GRAD_KEYS, c=C_BOUND, what=""):
+def assert_grads_bounded(got: dict, ref: dict, keys=GRAD_KEYS, c=C_BOUND, what="", rows=None):
     """Per-element bound |hip - ref| <= 1e-4 |ref| + c 2^-24 sum w|term| on EVERY element of every tensor; `ref` comes
-    from run_oracle / run_oracle_hdr(bounds=True).  Returns {tensor: (n_outside, c_needed)}."""
+    from run_oracle / run_oracle_hdr(bounds=True).  `rows`: bool [P] -- only those Gaussians are held to it (the clear rows
+    of a first pass, ~decision_masks()["rows"]: every pixel they were blended on took identical decisions on both sides).
+    Returns {tensor: (n_outside, c_needed)}."""
     rep = {}
     for gk, rk in keys:
         r = np.asarray(ref[rk], np.float64)
         g = np.asarray(got["d_" + gk], np.float64).reshape(r.shape)
         S = np.asarray(ref["abs_" + rk], np.float64).reshape(r.shape)
+        if rows is not None:
+            r, g, S = r[rows], g[rows], S[rows]
         unit = 2.0 ** -24 * S
         excess = np.abs(g - r) - 1e-4 * np.abs(r)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -519,7 +525,9 @@ def assert_grads_bounded(got: dict, ref: dict, keys=GRAD_KEYS, c=C_BOUND, what="
 
 
 def crf_grad_bound(sc: S.Scene, ref_imgs, dL_ldr, c=6.0):
-    """Per-entry bound of d(crf_table) [3,K] for the 'ldr' blur domain / a single pose: 1e-4 |ref| is added by the caller;
+    """Per-entry bound of d(crf_table) [3,K]: `ref_imgs` are the radiance images the CRF is applied to -- one per pose in the
+    'ldr' blur domain (each takes dL / N), the ONE mean image in the 'hdr' domain or for a single pose (it takes dL).
+    1e-4 |ref| is added by the caller;
     this is what the two implementations may differ by on identical decisions,
         c * (sigma_q sqrt(n_k) + delta_f sqrt(sum g^2)_k),
     n_k / (sum g^2)_k over the (pixel, pose) terms that touch entry k (a pixel between knots i, i + 1 adds (1 - f) g and
@@ -549,18 +557,53 @@ def crf_grad_bound(sc: S.Scene, ref_imgs, dL_ldr, c=6.0):
     return c * (q / np.sqrt(12.0) * np.sqrt(n_k) + delta_f * np.sqrt(s2_k))
 
 
-def masked_backward_pass(O, sc: S.Scene, masks, fwds, cameras=None, hdr=True, blur_domain="ldr", workers=1, what=""):
+def run_oracle_poses(O, sc: S.Scene, cameras, dL, fwds, radiance_activation="relu_shift", bounds=False, workers=1,
+                     use_cov_precomp=None, use_colors_precomp=None):
+    """Backward of the non-HDR N-pose frame (the linear-radiance blur: the output is the mean of the per-pose renders) with
+    the C oracle: sum over the poses, in pose order, of backward(dL / N) given each pose's forward in `fwds`; with
+    `bounds`, the abs_* magnitudes (and n_terms) are summed alongside."""
+    N = len(cameras)
+    dLn = (np.asarray(dL, np.float32) / np.float32(N)).astype(np.float32)
+    kw = {}
+    if use_colors_precomp is not None:
+        kw["colors_precomp"] = use_colors_precomp.numpy()
+    else:
+        kw["shs"] = sc.shs.numpy()
+    if use_cov_precomp is not None:
+        kw["cov3D_precomp"] = use_cov_precomp.numpy()
+    else:
+        kw.update(scales=sc.scales.numpy(), rotations=sc.rotations.numpy())
+
+    def one(k):
+        ocam = oracle_camera(O, sc, cameras[k], radiance_activation)
+        b = O.backward(ocam, fwds[k], dLn, sc.means3D.numpy(), bounds=bounds, **kw)
+        return {q: v for q, v in b.items() if q.startswith(("dL_d", "abs_dL_d", "n_terms")) and isinstance(v, np.ndarray)}
+
+    acc = None
+    for b in _pose_map(one, range(N), workers):
+        if acc is None:
+            acc = {q: v.astype(np.float64 if q != "n_terms" else np.int64) for q, v in b.items()}
+        else:
+            for q in acc:
+                acc[q] += b[q]
+    return {q: (v.astype(np.float32) if q != "n_terms" else v) for q, v in acc.items()}
+
+
+def masked_backward_pass(O, sc: S.Scene, masks, fwds, cameras=None, hdr=True, blur_domain="ldr", workers=1, what="",
+                         radiance_activation="relu_shift", use_cov_precomp=None, use_colors_precomp=None):
     """The second backward of VERDICT r4 next #2: dL zeroed on masks["excluded"] on BOTH sides (the HIP path renders and
     differentiates the frame again with the masked dL, the oracle reuses its forwards).  Returns (got, ref, dL_masked);
-    the caller holds EVERY row to its bar (no at_risk) and every element to assert_grads_bounded."""
+    the caller holds EVERY row to its bar (no at_risk) and every element to assert_grads_bounded.  Frames: HDR (one or N
+    poses, either blur domain), and linear radiance of one pose (precomputed colours / covariances allowed) or of N poses
+    (the mean of the per-pose renders: the oracle reference is sum_k backward(dL / N))."""
     dLm = np.asarray(sc.dL_dimage.numpy(), np.float32) * (~masks["excluded"])[None].astype(np.float32)
-    got = run_hip(sc, cameras=cameras, hdr=hdr, blur_domain=blur_domain, dL_image=dLm)
+    got = run_hip(sc, cameras=cameras, hdr=hdr, blur_domain=blur_domain, dL_image=dLm, radiance_activation=radiance_activation,
+                  use_cov_precomp=use_cov_precomp, use_colors_precomp=use_colors_precomp)
     if hdr:
-        ref = run_oracle_hdr(O, sc, cameras, blur_domain, dL_ldr=dLm, workers=workers, fwds=fwds, bounds=True)
+        assert use_cov_precomp is None and use_colors_precomp is None
+        ref = run_oracle_hdr(O, sc, cameras, blur_domain, dL_ldr=dLm, workers=workers, fwds=fwds, bounds=True,
+                             radiance_activation=radiance_activation)
     else:
-        assert cameras is None or len(cameras) == 1
-        cam = None if cameras is None else cameras[0]
-        ocam = oracle_camera(O, sc, cam)
-        ref = O.backward(ocam, fwds[0], dLm, sc.means3D.numpy(), shs=sc.shs.numpy(), scales=sc.scales.numpy(),
-                         rotations=sc.rotations.numpy(), bounds=True)
+        ref = run_oracle_poses(O, sc, cameras or [sc.camera], dLm, fwds, radiance_activation, bounds=True, workers=workers,
+                               use_cov_precomp=use_cov_precomp, use_colors_precomp=use_colors_precomp)
     return got, ref, dLm

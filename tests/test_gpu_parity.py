@@ -1716,9 +1716,12 @@ def test_randomized_configurations_vs_oracle(oracle):
     """Sweep of small random configurations (sizes that are not multiples of the tile or block sizes, every SH degree,
     1-3 poses, with and without the HDR epilogue, both blur domains, the three radiance activations, sync and
     fixed-capacity binning): structure bit-exact, images and
-    gradients within the numerical contract.  Catches indexing bugs that the handful of fixed shapes cannot."""
+    gradients within the numerical contract.  Catches indexing bugs that the handful of fixed shapes cannot.
+    Besides SWEEP_BAR's blanket fractions every case is held to the per-element bound: the first pass on its clear rows,
+    and the masked pass (_masked_pass) on every row.  Failures are collected over all cases and reported together."""
     # HS_SWEEP_SEED / HS_SWEEP_CASES: soak runs with other seeds and more cases (scripts/soak.sh)
     rng = np.random.default_rng(int(os.environ.get("HS_SWEEP_SEED", "2026")))
+    failures = []
     for case in range(int(os.environ.get("HS_SWEEP_CASES", "24"))):
         c = Hh.sweep_case(rng, case)
         # (these frames are small: by default their pairs are sorted by counting; one case in three keeps the radix passes,
@@ -1730,56 +1733,174 @@ def test_randomized_configurations_vs_oracle(oracle):
         os.environ.pop("HS_DEPTH_SORT", None)
         if case % 4 == 3:
             os.environ["HS_DEPTH_SORT"] = "lsd"
-        P, W, H, n_poses, hdr, act, dom = c["P"], c["W"], c["H"], c["n_poses"], c["hdr"], c["act"], c["dom"]
-        sc, cams, precomp, what = c["sc"], c["cams"], c["precomp"], c["what"]
-        if hdr or n_poses > 1:
-            if not hdr:  # linear-radiance blur: the average of the per-pose oracle renders
-                fs = [Hh.run_oracle(oracle, sc, cam=c, backward=False, radiance_activation=act)[0] for c in cams]
-                g = Hh.run_hip(sc, cameras=cams, backward=False, radiance_activation=act)
-                ref = np.mean(np.stack([f["color"] for f in fs]), axis=0, dtype=np.float64)
-                assert_image_close(g["color"], ref, what)
-                assert np.array_equal(g["radii"], np.max(np.stack([f["radii"] for f in fs]), axis=0)), what
-                continue
-            r = Hh.run_oracle_hdr(oracle, sc, cams, dom, radiance_activation=act)
-            Rtot = sum(f["R"] for f in r["fwd"])
-            g = Hh.run_hip(sc, cameras=cams, hdr=True, blur_domain=dom, capacity=None if case % 2 else Rtot + 7,
-                           radiance_activation=act)
-            st = g["state"]
-            assert st["num_rendered"] == Rtot, what
-            for k, f in enumerate(r["fwd"]):
-                check_structure(st, f, pose=k, P=P)
-            pl = np.concatenate([f["point_list"].astype(np.int64) + k * P for k, f in enumerate(r["fwd"])])
-            assert np.array_equal(u32(st["point_list"][:Rtot]), pl), what
-            # decisions may differ from the oracle's only on pixels inside its threshold guard band; every gradient row off
-            # the tile lists of the pixels where they DID differ (and off the pixels at a CRF knot) is held to the bar
-            n_p = len(r["fwd"])
-            got_imgs, ref_imgs = ([g["hdr"]], [r["hdr"]]) if (dom == "hdr" or n_p == 1) else \
-                (list(st["pose_hdr"][:n_p]), [f["color"] for f in r["fwd"]])
-            m = Hh.decision_masks(oracle, sc, r["fwd"], st, cams, crf_got=got_imgs, crf_ref=ref_imgs, what=what)
-            for k, f in enumerate(r["fwd"]):
-                check_image(st["pose_hdr"][k], f["color"], m, what, pose=k)
-            assert_image_close(g["hdr"], r["hdr"], what)
-            assert_image_close(g["color"], r["ldr"], what)
-            Hh.assert_grads_close(g, r, what=what, at_risk=m["rows"], **SWEEP_BAR)
-        else:
-            pre, keys = {}, Hh.GRAD_KEYS
-            if precomp:
-                f0 = Hh.run_oracle(oracle, sc, backward=False)[0]
-                pre = dict(use_colors_precomp=c["colors"], use_cov_precomp=torch.from_numpy(f0["cov3D"].copy()))
-                keys = [("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "dL_dopacity"),
-                        ("colors_precomp", "dL_dcolors_precomp"), ("cov3D_precomp", "dL_dcov3D")]
-            f, b = Hh.run_oracle(oracle, sc, radiance_activation=act, **pre)
-            g = Hh.run_hip(sc, capacity=None if case % 2 else f["R"] + 1, radiance_activation=act, **pre)
-            st = g["state"]
-            assert st["num_rendered"] == f["R"], what
-            check_structure(st, f)
-            assert np.array_equal(u32(st["offsets"]), u32(f["offsets"])), what
-            assert np.array_equal(u32(st["point_list"][:f["R"]]), u32(f["point_list"])), what
-            assert np.array_equal(u32(st["ranges"]), u32(f["ranges"])), what
-            m = Hh.decision_masks(oracle, sc, [f], st, what=what)
-            check_image(g["color"], f["color"], m, what)
-            Hh.assert_grads_close(g, b, keys=keys, what=what, at_risk=m["rows"], **SWEEP_BAR)
+        try:
+            _sweep_case_vs_oracle(oracle, c, case)
+        except AssertionError as e:
+            failures.append(f"{c['what']}: {e}")
+            if os.environ.get("HS_PARITY_REPORT"):
+                print("SWEEP FAILED", failures[-1], flush=True)
     os.environ.pop("HS_TILE_SORT", None)
+    os.environ.pop("HS_DEPTH_SORT", None)
+    assert not failures, f"{len(failures)} failing case(s):\n" + "\n".join(failures)
+
+
+def _sweep_case_vs_oracle(oracle, c, case, sweep_bar=True):
+    """One case of the sweep (helpers.sweep_case).  `sweep_bar` False: SWEEP_BAR is not applied to the first pass and its
+    relative-L2 term not to the masked pass (the fixed replay of a case whose L2 misses it by fp32 rounding:
+    test_sweep_seed24_case9_giant_footprint); structure, images and the per-element bound are."""
+    P, W, H, n_poses, hdr, act, dom = c["P"], c["W"], c["H"], c["n_poses"], c["hdr"], c["act"], c["dom"]
+    sc, cams, precomp, what = c["sc"], c["cams"], c["precomp"], c["what"]
+    # (the masked pass: every row on SWEEP_BAR; d_crf_table inside crf_grad_bound's per-entry bound, and within 2e-4 of
+    #  max(|ref|, RMS) -- small frames measure up to 1.7e-4 there, the glibc logf / v_log_f32 interval weights of a few
+    #  thousand pixels per knot)
+    mbar = dict(SWEEP_BAR if sweep_bar else dict(SWEEP_BAR, l2_tol=np.inf), crf_rel=2e-4)
+    if hdr or n_poses > 1:
+        if not hdr:  # linear-radiance blur: the average of the per-pose oracle renders
+            fs = [Hh.run_oracle(oracle, sc, cam=c, backward=False, radiance_activation=act)[0] for c in cams]
+            g = Hh.run_hip(sc, cameras=cams, radiance_activation=act)
+            ref = np.mean(np.stack([f["color"] for f in fs]), axis=0, dtype=np.float64)
+            assert_image_close(g["color"], ref, what)
+            assert np.array_equal(g["radii"], np.max(np.stack([f["radii"] for f in fs]), axis=0)), what
+            # ... and its gradients: sum over the poses of the oracle's backward of dL / N
+            st = g["state"]
+            Rtot = sum(f["R"] for f in fs)
+            assert st["num_rendered"] == Rtot, what
+            for k, f in enumerate(fs):
+                check_structure(st, f, pose=k, P=P)
+            pl = np.concatenate([f["point_list"].astype(np.int64) + k * P for k, f in enumerate(fs)])
+            assert np.array_equal(u32(st["point_list"][:Rtot]), pl), what
+            m = Hh.decision_masks(oracle, sc, fs, st, cams, what=what)
+            for k, f in enumerate(fs):
+                check_image(st["pose_hdr"][k], f["color"], m, what, pose=k)
+            r = Hh.run_oracle_poses(oracle, sc, cams, sc.dL_dimage.numpy(), fs, act, bounds=True)
+            if sweep_bar:
+                Hh.assert_grads_close(g, r, what=what, at_risk=m["rows"], **SWEEP_BAR)
+            Hh.assert_grads_bounded(g, r, what=what + " clear rows", rows=~m["rows"])
+            _masked_pass(oracle, sc, m, fs, what, cameras=cams, hdr=False, act=act, **mbar)
+            return
+        r = Hh.run_oracle_hdr(oracle, sc, cams, dom, radiance_activation=act, bounds=True)
+        Rtot = sum(f["R"] for f in r["fwd"])
+        g = Hh.run_hip(sc, cameras=cams, hdr=True, blur_domain=dom, capacity=None if case % 2 else Rtot + 7,
+                       radiance_activation=act)
+        st = g["state"]
+        assert st["num_rendered"] == Rtot, what
+        for k, f in enumerate(r["fwd"]):
+            check_structure(st, f, pose=k, P=P)
+        pl = np.concatenate([f["point_list"].astype(np.int64) + k * P for k, f in enumerate(r["fwd"])])
+        assert np.array_equal(u32(st["point_list"][:Rtot]), pl), what
+        # decisions may differ from the oracle's only on pixels inside its threshold guard band; every gradient row off
+        # the tile lists of the pixels where they DID differ (and off the pixels at a CRF knot) is held to the bar
+        n_p = len(r["fwd"])
+        got_imgs, ref_imgs = ([g["hdr"]], [r["hdr"]]) if (dom == "hdr" or n_p == 1) else \
+            (list(st["pose_hdr"][:n_p]), [f["color"] for f in r["fwd"]])
+        m = Hh.decision_masks(oracle, sc, r["fwd"], st, cams, crf_got=got_imgs, crf_ref=ref_imgs, what=what)
+        for k, f in enumerate(r["fwd"]):
+            check_image(st["pose_hdr"][k], f["color"], m, what, pose=k)
+        assert_image_close(g["hdr"], r["hdr"], what)
+        assert_image_close(g["color"], r["ldr"], what)
+        if sweep_bar:
+            Hh.assert_grads_close(g, r, what=what, at_risk=m["rows"], **SWEEP_BAR)
+        Hh.assert_grads_bounded(g, r, what=what + " clear rows", rows=~m["rows"])
+        _masked_pass(oracle, sc, m, r["fwd"], what, cameras=cams, blur_domain=dom, act=act, **mbar)
+    else:
+        pre, keys = {}, Hh.GRAD_KEYS
+        if precomp:
+            f0 = Hh.run_oracle(oracle, sc, backward=False)[0]
+            pre = dict(use_colors_precomp=c["colors"], use_cov_precomp=torch.from_numpy(f0["cov3D"].copy()))
+            keys = [("means3D", "dL_dmeans3D"), ("means2D", "dL_dmeans2D"), ("opacities", "dL_dopacity"),
+                    ("colors_precomp", "dL_dcolors_precomp"), ("cov3D_precomp", "dL_dcov3D")]
+        f, b = Hh.run_oracle(oracle, sc, radiance_activation=act, bounds=True, **pre)
+        g = Hh.run_hip(sc, capacity=None if case % 2 else f["R"] + 1, radiance_activation=act, **pre)
+        st = g["state"]
+        assert st["num_rendered"] == f["R"], what
+        check_structure(st, f)
+        assert np.array_equal(u32(st["offsets"]), u32(f["offsets"])), what
+        assert np.array_equal(u32(st["point_list"][:f["R"]]), u32(f["point_list"])), what
+        assert np.array_equal(u32(st["ranges"]), u32(f["ranges"])), what
+        m = Hh.decision_masks(oracle, sc, [f], st, what=what)
+        check_image(g["color"], f["color"], m, what)
+        if sweep_bar:
+            Hh.assert_grads_close(g, b, keys=keys, what=what, at_risk=m["rows"], **SWEEP_BAR)
+        Hh.assert_grads_bounded(g, b, keys=keys, what=what + " clear rows", rows=~m["rows"])
+        _masked_pass(oracle, sc, m, [f], what, hdr=False, act=act, keys=keys, **pre, **mbar)
+
+
+def test_sweep_seed24_case9_giant_footprint(oracle):
+    """Soak seed 24, case 9 as a fixed test: a 28 x 161 HDR frame ("wild", e^s radiance, 'hdr' blur domain) with one
+    exp-bright Gaussian of radius 2738 px whose d_means3D misses SWEEP_BAR's relative L2 (3.3e-5 against 2e-5): the row of
+    that one Gaussian sums thousands of random-sign pixel terms in fp32 and IS most of the tensor's norm.  Structure bit
+    for bit, images, and every element -- clear rows of the first pass, every row of the masked pass -- inside the
+    per-element bound, which is what separates rounding of a long sum from a wrong record."""
+    rng = np.random.default_rng(24)
+    for case in range(10):
+        c = Hh.sweep_case(rng, case)
+    assert c["what"].startswith("case 9: P=1085 28x161 deg=1 poses=1 hdr=True seed=999 act=exp dom=hdr"), c["what"]
+    assert "wild=True" in c["what"]
+    os.environ.pop("HS_TILE_SORT", None)
+    os.environ.pop("HS_DEPTH_SORT", None)
+    f = Hh.run_oracle(oracle, c["sc"], backward=False, radiance_activation="exp")[0]
+    assert f["radii"].max() > 2500                      # the giant footprint is there
+    _sweep_case_vs_oracle(oracle, c, 9, sweep_bar=False)
+
+
+# (rows on the first pass's strict bar, measured on the MI355X: each scene's own share less half a per cent)
+EXTREME_SHARE = {"floaters": 0.965, "near_plane": 0.995, "off_screen": 0.98, "opaque_stack": 0.98,
+                 "floaters_8_poses": 0.88}   # (measured 0.9702, 1.0, 0.9858, 0.9845, 0.8864)
+
+
+@pytest.mark.parametrize("name", ["floaters", "near_plane", "off_screen", "opaque_stack", "floaters_8_poses"])
+def test_extreme_geometry_vs_oracle(oracle, name):
+    """synthetic.extreme_scene: footprints that cover a 1080p frame (instance runs of 8160 tile records summed by one
+    pair_segsum run), Gaussians at the near plane, centres frames away off screen, opaque stacks that terminate at varied
+    depths; and the floaters seen from eight rotating poses.  (Not here: needles -- scale ratios of 1e3-1e4 put the thin axis
+    at the 0.3 px dilation floor, and the power -0.5 d^T conic d then cancels terms of up to ~1e6 to a few units, so the
+    FMA-contracted kernel and the oracle decide alpha >= 1/255 differently on pixels outside oracle.threshold_risk's guard
+    band, which assumes a well-conditioned power: 13 pixels of a 960 x 540 frame.  The guard band needs the power's
+    conditioning first.)  Structure bit for bit against
+    the oracle, images off the pixels where a decision differs, gradients on the at-risk bars with the clear rows inside the
+    per-element bound, and the masked pass: every row on the bar, every element inside the bound."""
+    base = name.replace("_8_poses", "")
+    sc = S.extreme_scene(base)
+    hdr = base == "floaters"
+    P = sc.means3D.shape[0]
+    cams = S.perturbed_poses(sc.camera, 8, seed=5, rot_step_deg=0.05, step=0.01) if name.endswith("_8_poses") else None
+    ncam = 1 if cams is None else len(cams)
+    workers = min(ncam, os.cpu_count() or 1, 8)
+    if hdr:
+        r = Hh.run_oracle_hdr(oracle, sc, cams, "ldr", workers=workers, bounds=True)
+        fwds = r["fwd"]
+    else:
+        f, r = Hh.run_oracle(oracle, sc, bounds=True)
+        fwds = [f]
+    g = Hh.run_hip(sc, cameras=cams, hdr=hdr)
+    st = g["state"]
+    Rs = [f["R"] for f in fwds]
+    assert st["num_rendered"] == sum(Rs), name
+    assert max(int(f["tiles_touched"].max()) for f in fwds) >= (8160 if base == "floaters" else 500), name
+    pl = np.concatenate([f["point_list"].astype(np.int64) + k * P for k, f in enumerate(fwds)])
+    assert np.array_equal(u32(st["point_list"][:sum(Rs)]), pl), name
+    for k, f in enumerate(fwds):
+        check_structure(st, f, pose=k, P=P)
+    if cams is None:
+        assert np.array_equal(u32(st["ranges"]), u32(fwds[0]["ranges"])), name
+    crf = {}
+    if hdr:
+        crf = dict(crf_got=[g["hdr"]], crf_ref=[r["hdr"]]) if cams is None else \
+            dict(crf_got=list(st["pose_hdr"][:ncam]), crf_ref=[f["color"] for f in fwds])
+    m = Hh.decision_masks(oracle, sc, fwds, st, cams, what=name, workers=workers, **crf)
+    for k, f in enumerate(fwds):
+        img = g["color"] if not hdr else (g["hdr"] if cams is None else st["pose_hdr"][k])
+        check_image(img, f["color"], m, name + f" pose {k}", pose=k)
+        check_image(st["final_T"][k], f["final_T"], m, name + f" final_T {k}", pose=k)
+    if hdr:
+        assert_image_close(g["color"], r["ldr"], name)
+    Hh.assert_grads_close(g, r, what=name, at_risk=m["rows"], min_strict=EXTREME_SHARE[name], max_tol=2e-2)
+    Hh.assert_grads_bounded(g, r, what=name + " clear rows", rows=~m["rows"])
+    # (d_crf_table of the single-pose floaters: 1.09e-4 of max(|ref|, RMS) measured -- the glibc logf / v_log_f32 interval
+    #  weight term of crf_grad_bound grows with sqrt(sum g^2) over two million saturated pixels; the stated per-entry bound
+    #  holds every entry)
+    _masked_pass(oracle, sc, m, fwds, name, cameras=cams, workers=workers, hdr=hdr, frac_tol=2e-3, max_tol=2e-2,
+                 l2_tol=5e-6, crf_rel=2e-4)
 
 
 def test_c_abi_from_a_plain_cpp_host(tmp_path, oracle):
@@ -1906,21 +2027,28 @@ def _parity_row(name, sc, m, g, r, extra=None, masked=None):
     json.dump(old, open(path, "w"), indent=1)
 
 
-def _masked_pass(oracle, sc, m, fwds, what, cameras=None, workers=1, frac_tol=1e-3, max_tol=1e-2, l2_tol=2e-6):
+def _masked_pass(oracle, sc, m, fwds, what, cameras=None, workers=1, frac_tol=1e-3, max_tol=1e-2, l2_tol=2e-6, hdr=True,
+                 blur_domain="ldr", act="relu_shift", keys=Hh.GRAD_KEYS, use_colors_precomp=None, use_cov_precomp=None,
+                 crf_rel=1e-4):
     """the second backward with dL zeroed on the pixels where a decision differed and on the CRF-knot
     pixels, on BOTH sides.  No row is excused: every Gaussian on the (full-size) bar, every element inside
-    1e-4 |ref| + C_BOUND 2^-24 sqrt(n) sum|terms| (zero outside), CRF-table / exposure gradients against the oracle's
+    1e-4 |ref| + C_BOUND 2^-24 sqrt(n) sum|terms| (zero outside), CRF-table / exposure gradients (hdr) against the oracle's
     own within 1e-4 of max(|ref|, tensor RMS) and inside the stated fixed-point + interval-weight bound."""
-    g2, r2, dLm = Hh.masked_backward_pass(oracle, sc, m, fwds, cameras=cameras, workers=workers, what=what)
-    rep = Hh.assert_grads_close(g2, r2, what=what + " masked", frac_tol=frac_tol, max_tol=max_tol, l2_tol=l2_tol)
-    bounded = Hh.assert_grads_bounded(g2, r2, what=what + " masked")
+    g2, r2, dLm = Hh.masked_backward_pass(oracle, sc, m, fwds, cameras=cameras, hdr=hdr, blur_domain=blur_domain,
+                                          workers=workers, what=what, radiance_activation=act,
+                                          use_colors_precomp=use_colors_precomp, use_cov_precomp=use_cov_precomp)
+    rep = Hh.assert_grads_close(g2, r2, keys=keys, what=what + " masked", frac_tol=frac_tol, max_tol=max_tol, l2_tol=l2_tol)
+    bounded = Hh.assert_grads_bounded(g2, r2, keys=keys, what=what + " masked")
+    if not hdr:
+        return g2, r2, bounded, rep
     tab = np.asarray(r2["dL_dcrf_table"], np.float64)
     err = np.abs(np.asarray(g2["d_crf_table"], np.float64) - tab)
-    rms = float(np.sqrt((tab ** 2).mean()))
-    assert float((err / np.maximum(np.abs(tab), rms)).max()) <= 1e-4, (what, "d_crf_table", float((err / np.maximum(np.abs(tab), rms)).max()))
-    imgs = [f["color"] for f in fwds]
+    # (the images the CRF is applied to: every pose's in the 'ldr' blur domain, the ONE mean image in the 'hdr' domain)
+    imgs = [r2["hdr"]] if blur_domain == "hdr" else [f["color"] for f in fwds]
     bound = 1e-4 * np.abs(tab) + Hh.crf_grad_bound(sc, imgs, dLm)
     assert not (err > bound).any(), (what, "d_crf_table entries outside the stated bound", int((err > bound).sum()), float((err / bound).max()))
+    rms = float(np.sqrt((tab ** 2).mean()))
+    assert float((err / np.maximum(np.abs(tab), rms)).max()) <= crf_rel, (what, "d_crf_table", float((err / np.maximum(np.abs(tab), rms)).max()))
     assert float(g2["d_exposure"]) == pytest.approx(r2["dL_dexposure"], rel=1e-4, abs=1e-4 * float(np.abs(dLm).sum()) * 1e-3)
     return g2, r2, bounded, rep
 
