@@ -83,8 +83,15 @@ class hs_layout(C.Structure):
         "tile_matrix", "hier_ws", "depth_ws")]
 
 
+class hs_loss_args(C.Structure):
+    _fields_ = [("planes", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("lambda_dssim", C.c_float),
+                ("image", _fp), ("target", _fp), ("workspace", _fp), ("partials", _fp), ("out", _fp),
+                ("dL_dloss", _fp), ("dL_dimage", _fp)]
+
+
 EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
-           "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort")
+           "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
+           "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward")
 HS_RENDER_STATS = 24
 
 _lib = None
@@ -131,6 +138,12 @@ def load() -> C.CDLL:
     lib.hs_sort_tickets.restype = C.c_int
     lib.hs_depth_sort.argtypes = [C.c_int]
     lib.hs_depth_sort.restype = C.c_int
+    lib.hs_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    lib.hs_loss_workspace_bytes.restype = C.c_int64
+    lib.hs_photometric_loss.argtypes = [C.POINTER(hs_loss_args), C.c_void_p]
+    lib.hs_photometric_loss.restype = C.c_int
+    lib.hs_photometric_loss_backward.argtypes = [C.POINTER(hs_loss_args), C.c_void_p]
+    lib.hs_photometric_loss_backward.restype = C.c_int
     _lib = lib
     return lib
 

@@ -231,6 +231,19 @@ static int check_flags(int flags, const char* who) {
     return HS_OK;
 }
 
+// hs_loss_args limits: planes, H, W >= 1, planes * H * W < 2^31, 0 <= lambda <= 1 (NaN rejected)
+static int check_loss_shape(int32_t planes, int32_t H, int32_t W, float lambda, const char* who) {
+    if (planes < 1 || H < 1 || W < 1 || (int64_t)planes * H * W >= (1ll << 31)) {
+        set_error("%s: bad shape planes=%d H=%d W=%d (each >= 1, planes * H * W < 2^31)", who, planes, H, W);
+        return HS_EINVAL;
+    }
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) {
+        set_error("%s: lambda_dssim=%g outside [0, 1]", who, (double)lambda);
+        return HS_EINVAL;
+    }
+    return HS_OK;
+}
+
 }  // namespace hs
 
 using namespace hs;
@@ -448,6 +461,35 @@ int hs_render_stats(const hs_fwd_args* fwd, const hs_bwd_args* bwd, uint64_t* st
         if (bwd->dims.P > 0 && (rc = launch_render_bwd(*bwd, L, s, (unsigned long long*)stats, (unsigned long long*)bwd_timeline))) return rc;
     }
     return HS_OK;
+}
+
+int64_t hs_loss_workspace_bytes(int32_t planes, int32_t H, int32_t W, int32_t with_partials) {
+    if (check_loss_shape(planes, H, W, 0.0f, "hs_loss_workspace_bytes")) return HS_EINVAL;
+    const int64_t pairs = align_up(loss_pair_count(planes, H, W) * 16, 256);
+    return pairs + (with_partials ? (int64_t)12 * planes * H * W : 0);
+}
+
+int hs_photometric_loss(const hs_loss_args* a, void* hip_stream) {
+    if (!a) { set_error("hs_photometric_loss: null args"); return HS_EINVAL; }
+    int rc = check_loss_shape(a->planes, a->H, a->W, a->lambda_dssim, "hs_photometric_loss");
+    if (rc) return rc;
+    if (!a->image || !a->target || !a->workspace || !a->out) {
+        set_error("hs_photometric_loss: null image/target/workspace/out");
+        return HS_EINVAL;
+    }
+    if ((uintptr_t)a->workspace & 255) { set_error("hs_photometric_loss: workspace must be 256-byte aligned"); return HS_EINVAL; }
+    return launch_loss_fwd(*a, (hipStream_t)hip_stream);
+}
+
+int hs_photometric_loss_backward(const hs_loss_args* a, void* hip_stream) {
+    if (!a) { set_error("hs_photometric_loss_backward: null args"); return HS_EINVAL; }
+    int rc = check_loss_shape(a->planes, a->H, a->W, a->lambda_dssim, "hs_photometric_loss_backward");
+    if (rc) return rc;
+    if (!a->image || !a->target || !a->partials || !a->dL_dloss || !a->dL_dimage) {
+        set_error("hs_photometric_loss_backward: null image/target/partials/dL_dloss/dL_dimage");
+        return HS_EINVAL;
+    }
+    return launch_loss_bwd(*a, (hipStream_t)hip_stream);
 }
 
 int64_t hs_sort_tmp_bytes(int64_t n) { return sort_tmp_bytes(n) + 256 + 2 * align_up(n * 8, 256) + 2 * align_up(n * 4, 256); }

@@ -102,6 +102,10 @@ int launch_spline_poses(int J, int T, int kind, const float* delta, const float*
                         float* jac, int* seg, hipStream_t s);
 int launch_sh_backward_views(int P, int M, int deg, int V, const float* means3D, const float* camposes,
                              const float* view_colors, float* d_shs, hipStream_t s);
+// photometric loss (loss.hip): tiles of the forward = pairs in the workspace
+int64_t loss_pair_count(int planes, int H, int W);
+int launch_loss_fwd(const hs_loss_args& a, hipStream_t s);
+int launch_loss_bwd(const hs_loss_args& a, hipStream_t s);
 
 // Scratch of the single-sweep radix passes (binning.hip): digit totals in kGhistCopies copies of [pass <= 8][256], one
 // ticket counter per pass (a block's place in the look-back chain), then one status word per (pass, block, digit).

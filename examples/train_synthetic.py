@@ -9,6 +9,7 @@ Adam against the observations -- what /root/reference/Readme.md:54 describes ("j
 camera motion") -- through the HIP kernels: every step is frames x (N-pose forward + backward).
 
     python examples/train_synthetic.py --steps 300
+    python examples/train_synthetic.py --steps 300 --lambda-dssim 0.2     # the published L1 + D-SSIM loss, fused
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -25,6 +26,7 @@ sys.path.insert(0, ROOT)
 import torch
 
 from casualhdrsplat_amd import synthetic as S
+from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.graphs import GraphedStep
 from casualhdrsplat_amd.image_formation import (FrameRasterizers, HDRBlurFormation, ImplicitCRF, TrajectorySpline,
                                                   knots_from_lookat)
@@ -50,8 +52,10 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
-        graph=False, capacity=None):
-    """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks)."""
+        graph=False, capacity=None, lambda_dssim=0.0):
+    """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
+    lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
+    losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1."""
     dev = torch.device(device)
     sc = S.make_scene(P, W, H, deg, seed=seed, hdr=True)
     cam = sc.camera
@@ -112,7 +116,10 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         losses, mses = [], []
         for i in range(frames):
             ldr, _, _, _ = model(i, fixed["means3D"], opac, shs, fixed["scales"], fixed["rotations"], cameras=cams)
-            losses.append(mean_by_rows((ldr - targets[i]).abs()))
+            if lambda_dssim > 0:
+                losses.append(photometric_loss(ldr, targets[i], lambda_dssim))
+            else:
+                losses.append(mean_by_rows((ldr - targets[i]).abs()))
             mses.append(mean_by_rows((ldr.detach() - targets[i]) ** 2))
         torch.stack(losses).sum().backward()
         return torch.stack([l_.detach() for l_ in losses]), torch.stack(mses)
@@ -144,7 +151,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         e_dt, e_pose = errors()
         hist.append(dict(step=it, loss=total / frames, psnr=ps / frames, exposure_log_err=e_dt, knot_pos_err=e_pose))
         if not quiet and (it % log_every == 0 or it == steps):
-            print(f"step {it:4d}  L1 {total / frames:.5f}  PSNR {ps / frames:6.2f} dB  |log dt - truth| {e_dt:.4f}  "
+            print(f"step {it:4d}  {'L1' if lambda_dssim == 0 else 'loss'} {total / frames:.5f}  PSNR {ps / frames:6.2f} dB  |log dt - truth| {e_dt:.4f}  "
                   f"knot position error {e_pose:.5f}  ({(time.time() - t0) / max(it, 1) * 1e3:.1f} ms/step)")
     return dict(first=hist[0], last=hist[-1], history=hist)
 
@@ -160,8 +167,10 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--deg", type=int, default=1)
     ap.add_argument("--graph", action="store_true", help="record the gradient computation once as a HIP graph and replay it")
+    ap.add_argument("--lambda-dssim", type=float, default=0.0,
+                    help="weight of the D-SSIM term of the published 3DGS loss (0.2 upstream; 0 = plain L1)")
     a = ap.parse_args(argv)
-    r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph)
+    r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

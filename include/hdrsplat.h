@@ -336,6 +336,33 @@ HS_API int hs_depth_sort(int mode);
  * which it asks for the step again). */
 HS_API int hs_sort_tickets(int enable);
 
+/* (HS_VERSION 308, detected by name) Photometric training loss of the published 3DGS train.py, fused (loss.hip):
+ *   loss = (1 - lambda_dssim) * mean|image - target| + lambda_dssim * (1 - mean SSIM(image, target))
+ * SSIM as the published ssim(): 11 x 11 Gaussian window (sigma 1.5), zero padding, C1 = 0.01^2, C2 = 0.03^2, averaged over
+ * every plane (one channel of one image) and pixel.  All pointers are device memory owned by the caller; 256-byte aligned
+ * workspace.  Limits (HS_EINVAL): planes, H, W >= 1, planes * H * W < 2^31, 0 <= lambda_dssim <= 1. */
+typedef struct hs_loss_args {
+    int32_t planes, H, W;         /* images are [planes, H, W] fp32, contiguous ([B, C, H, W]: planes = B * C) */
+    float lambda_dssim;
+    const float* image;
+    const float* target;
+    void* workspace;              /* hs_loss_workspace_bytes(planes, H, W, 0) bytes: one fp64 pair per tile of the forward */
+    float* partials;              /* [3, planes, H, W] per-pixel partials of SSIM that the backward reads, or NULL: forward
+                                     only (evaluation, metrics) -- nothing to keep for a backward */
+    float* out;                   /* [3] written by the forward: {loss, l1_mean, ssim_mean} */
+    const float* dL_dloss;        /* [1] upstream gradient of the loss scalar (backward; read on the device, never the host) */
+    float* dL_dimage;             /* [planes, H, W] written by the backward */
+} hs_loss_args;
+
+/* Bytes of one buffer that holds the workspace (at offset 0) and, with with_partials != 0, the partials after it (at offset
+ * hs_loss_workspace_bytes(planes, H, W, 0)): align256(16 * tiles) + (with_partials ? 12 * planes * H * W : 0), tiles =
+ * planes * ceil(H / 16) * ceil(W / 64).  -1 (HS_EINVAL) for shapes outside the limits above. */
+HS_API int64_t hs_loss_workspace_bytes(int32_t planes, int32_t H, int32_t W, int32_t with_partials);
+/* forward: writes out[3] (and the partials when non-NULL); no atomics, the same inputs give the same bits */
+HS_API int hs_photometric_loss(const hs_loss_args* args, void* hip_stream);
+/* backward: dL_dimage = dL_dloss[0] * d loss / d image, from the partials of the forward of the same image / target */
+HS_API int hs_photometric_loss_backward(const hs_loss_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
