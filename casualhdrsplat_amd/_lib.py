@@ -8,10 +8,12 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("HS_LIB_PATH", os.path.join(_HERE, "libhdrsplat.so"))
 
+HS_VERSION = 309  # the hdrsplat.h whose structs the classes below mirror: load() refuses a library of another version
 HS_OK, HS_EINVAL, HS_EHIP, HS_EOVERFLOW = 0, -1, -2, -3
 HS_STAGE_PREPROCESS, HS_STAGE_BIN, HS_STAGE_RENDER, HS_STAGE_ALL, HS_STAGE_OFFSETS = 1, 2, 4, 7, 8
 HS_STAGE_PREPROCESS_ONLY = 16
@@ -20,6 +22,11 @@ HS_FLAG_RADIANCE_EXP, HS_FLAG_RADIANCE_SOFTPLUS = 16, 32
 HS_BWD_RENDER, HS_BWD_PREPROCESS, HS_BWD_CRF, HS_BWD_ALL = 1, 2, 4, 7
 HS_BWD_SEGSUM, HS_BWD_PROJECT = 8, 16
 HS_TILE = 16
+# hs_fwd_args.tile_sort / depth_sort / chain_order / emission_scan (0 = auto in each)
+HS_TILE_SORT_RADIX, HS_TILE_SORT_COUNT, HS_TILE_SORT_HIER = 1, 2, 3
+HS_DEPTH_SORT_PASSES, HS_DEPTH_SORT_COUNT = 1, 2
+HS_CHAIN_BLOCKIDX, HS_CHAIN_TICKETS = 1, 2
+HS_EMISSION_SCAN_AHEAD, HS_EMISSION_SCAN_INSIDE = 1, 2
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
 
@@ -49,6 +56,8 @@ class hs_fwd_args(C.Structure):
         ("rotations", _fp), ("cov3D_precomp", _fp), ("exposure", _fp), ("crf_table", _fp),
         ("geom", _fp), ("binning", _fp), ("image", _fp),
         ("out_color", _fp), ("out_hdr", _fp), ("radii", _fp), ("out_invdepth", _fp), ("counters_host", _fp),
+        ("tile_sort", C.c_int32), ("depth_sort", C.c_int32), ("chain_order", C.c_int32), ("emission_scan", C.c_int32),
+        ("depth_range_cap", C.c_int32), ("depth_dist_max", C.c_int32),
     ]
 
 
@@ -112,6 +121,9 @@ def load() -> C.CDLL:
         if not hasattr(lib, name):
             raise RuntimeError(f"{LIB_PATH} does not export {name}")
     lib.hs_version.restype = C.c_int
+    if lib.hs_version() != HS_VERSION:   # (a stale variant picked by HS_LIB_PATH would read the structs short or long)
+        raise RuntimeError(f"{LIB_PATH} is HS_VERSION {lib.hs_version()}, this package mirrors the structs of "
+                           f"{HS_VERSION}: rebuild it (`make -C casualhdrsplat_amd/csrc`)")
     lib.hs_last_error.restype = C.c_char_p
     lib.hs_plan.argtypes = [C.POINTER(hs_dims), C.POINTER(hs_sizes), C.POINTER(hs_layout)]
     lib.hs_plan.restype = C.c_int
@@ -144,8 +156,45 @@ def load() -> C.CDLL:
     lib.hs_photometric_loss.restype = C.c_int
     lib.hs_photometric_loss_backward.argtypes = [C.POINTER(hs_loss_args), C.c_void_p]
     lib.hs_photometric_loss_backward.restype = C.c_int
+    if os.environ.get("HS_SORT_TICKETS", "")[:1] == "1":   # the process default of the chain order, set once
+        lib.hs_sort_tickets(1)
     _lib = lib
     return lib
+
+
+def _atoi(s: str) -> int:
+    m = re.match(r"\s*[+-]?\d+", s)
+    return int(m.group()) if m else 0
+
+
+def sort_options(env) -> dict:
+    """The sort selection fields of hs_fwd_args that the switches in `env` (a mapping like os.environ) ask for.  The
+    library itself reads no environment: HS_TILE_SORT=radix / count / hier and HS_DEPTH_SORT=lsd / msd (first letter
+    counts), HS_SCAN_IN_EMISSION=1 / anything else, HS_DEPTH_RANGE_CAP and HS_DEPTH_DIST_MAX (integers) mean what they
+    meant when it did; unset = 0 = the library's own choice."""
+    cap, dist = env.get("HS_DEPTH_RANGE_CAP"), env.get("HS_DEPTH_DIST_MAX")
+    scan = env.get("HS_SCAN_IN_EMISSION")
+    return dict(
+        tile_sort={"r": HS_TILE_SORT_RADIX, "c": HS_TILE_SORT_COUNT, "h": HS_TILE_SORT_HIER}.get(env.get("HS_TILE_SORT", "")[:1], 0),
+        depth_sort={"l": HS_DEPTH_SORT_PASSES, "m": HS_DEPTH_SORT_COUNT}.get(env.get("HS_DEPTH_SORT", "")[:1], 0),
+        emission_scan=0 if scan is None else (HS_EMISSION_SCAN_INSIDE if scan[:1] == "1" else HS_EMISSION_SCAN_AHEAD),
+        # (the fields keep 0 for "not set": a set variable is clamped here, to [64, 4096] elements -- 4096 is all the LDS
+        # holds -- and to [0, 16] members with -1 for "0", as the library clamped what atoi gave it)
+        depth_range_cap=0 if cap is None else min(max(_atoi(cap), 64), 4096),
+        depth_dist_max=0 if dist is None else (-1 if _atoi(dist) <= 0 else min(_atoi(dist), 16)))
+
+
+def forward(a: hs_fwd_args, stream, what: str = "hs_forward") -> int:
+    """hs_forward(a) with the sort selection of the moment: os.environ's switches (sort_options) and, as an explicit value,
+    the process-wide chain order (hs_sort_tickets) -- returned, 1 = tickets: what the call is given is what the caller
+    knows it had.  Every hs_fwd_args the package hands to the library goes through here."""
+    lib = load()
+    for k, v in sort_options(os.environ).items():
+        setattr(a, k, v)
+    tickets = lib.hs_sort_tickets(-1)
+    a.chain_order = HS_CHAIN_TICKETS if tickets else HS_CHAIN_BLOCKIDX
+    check(lib.hs_forward(C.byref(a), stream), what)
+    return tickets
 
 
 def check(rc: int, what: str) -> None:

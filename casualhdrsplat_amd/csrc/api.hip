@@ -26,71 +26,57 @@ int fault_injection() {
 }
 #endif
 
-// Chain positions of the radix passes: blockIdx (default) or start-order tickets.  Process-wide, switchable at run time
-// (hs_sort_tickets): the host turns tickets on when a pass reports a stalled chain (hs_counters.overflow = 2).
-static std::atomic<int> g_sort_tickets{-1};
-bool sort_tickets() {
-    int v = g_sort_tickets.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = getenv("HS_SORT_TICKETS");
-        v = (e && e[0] == '1') ? 1 : 0;
-        int expected = -1;
-        if (!g_sort_tickets.compare_exchange_strong(expected, v)) v = expected;
-    }
-    return v != 0;
-}
-
+// Process defaults that a forward's sort fields consult where they say "auto" (hs_sort_tickets, hs_depth_sort): each read
+// at most once per hs_forward, by resolve_sorts.
+// Chain positions of the radix passes: blockIdx (0, default) or start-order tickets (1).  The host turns tickets on when a
+// pass reports a stalled chain (hs_counters.overflow = 2).
+static std::atomic<int> g_sort_tickets{0};
 // Depth sort of small frames: counting pass + range sorts (1) or the look-back passes (0); -1 = not set, the default.
 #ifndef HS_TUNE_DEPTH_MSD_DEFAULT
 #define HS_TUNE_DEPTH_MSD_DEFAULT 1
 #endif
 static std::atomic<int> g_depth_sort{-1};
-int depth_sort_mode(int64_t I) {
-    if (!depth_msd_fits(I)) return kDepthSortLsd;
-    const char* e = getenv("HS_DEPTH_SORT");   // (read at every forward: the test suite switches it inside one process)
-    if (e && e[0] == 'l') return kDepthSortLsd;
-    if (e && e[0] == 'm') return kDepthSortMsd;
-    const int v = g_depth_sort.load(std::memory_order_relaxed);
-    return v >= 0 ? v : (HS_TUNE_DEPTH_MSD_DEFAULT ? kDepthSortMsd : kDepthSortLsd);
-}
-int depth_range_cap() {
-    const char* e = getenv("HS_DEPTH_RANGE_CAP");
-    const int v = e ? atoi(e) : kMsdCap;
-    return v < 64 ? 64 : (v > kMsdCap ? kMsdCap : v);
-}
-
-int depth_dist_max() {
-    const char* e = getenv("HS_DEPTH_DIST_MAX");
-    const int v = e ? atoi(e) : 16;
-    return v < 0 ? 0 : (v > 16 ? 16 : v);
-}
-
-bool scan_in_emission(int64_t I) {
-    // (read at every forward, not once: the driver's test suite switches it inside one process)
-    const char* e = getenv("HS_SCAN_IN_EMISSION");
-    const int forced = e ? (e[0] == '1' ? 1 : 0) : -1;
-    // (the scan inside the emission is a blockIdx-ordered look-back chain like the radix passes': once the process has gone
-    // to ticket order -- a chain stalled, several processes share the GPU -- the offsets come from the three kernels ahead
-    // of the emission, which wait for nobody)
-    return forced >= 0 ? forced == 1 : (I >= (2 << 20) && !sort_tickets());
-}
-
 // A/B switch: large frames (those the counting sort does not take) get the hierarchical tile sort by default
 #ifndef HS_TUNE_HIER_DEFAULT
 #define HS_TUNE_HIER_DEFAULT 1
 #endif
-int tile_sort_mode(int64_t I, int64_t gx, int64_t gy, int64_t n_poses, int64_t capacity) {
-    const char* e = getenv("HS_TILE_SORT");   // (read at every forward: the test suite switches it inside one process)
-    const char f = e ? e[0] : 0;
-    const bool can_count = HS_TUNE_COUNT_SORT && count_sort_fits(I, gx * gy * n_poses, capacity);
-    const bool can_hier = hier_fits(I, gx, gy, n_poses, capacity);
-    if (f == 'r') return kTileSortRadix;
-    if (f == 'h' && can_hier) return kTileSortHier;
-    if (f == 'c') return can_count ? kTileSortCount : kTileSortRadix;
-    if (can_count) return kTileSortCount;
-    return (HS_TUNE_HIER_DEFAULT && can_hier) ? kTileSortHier : kTileSortRadix;
-}
 
+// The sorts of one forward (hs_common.h, SortChoice) from the call's fields, the process defaults and the dims.  Called once
+// per hs_forward, before anything is enqueued.
+static int resolve_sorts(const hs_fwd_args& a, SortChoice* c) {
+    if (a.tile_sort < 0 || a.tile_sort > HS_TILE_SORT_HIER || a.depth_sort < 0 || a.depth_sort > HS_DEPTH_SORT_COUNT ||
+        a.chain_order < 0 || a.chain_order > HS_CHAIN_TICKETS || a.emission_scan < 0 || a.emission_scan > HS_EMISSION_SCAN_INSIDE ||
+        a.depth_range_cap < 0 || a.depth_dist_max < -1) {
+        set_error("hs_forward: sort selection out of range (tile_sort=%d depth_sort=%d chain_order=%d emission_scan=%d "
+                  "depth_range_cap=%d depth_dist_max=%d; see hs_fwd_args in hdrsplat.h)", a.tile_sort, a.depth_sort,
+                  a.chain_order, a.emission_scan, a.depth_range_cap, a.depth_dist_max);
+        return HS_EINVAL;
+    }
+    const hs_dims& d = a.dims;
+    const int64_t I = (int64_t)d.P * d.n_poses;
+    const int64_t gx = (d.W + kTile - 1) / kTile, gy = (d.H + kTile - 1) / kTile;
+    const bool can_count = HS_TUNE_COUNT_SORT && count_sort_fits(I, gx * gy * d.n_poses, d.capacity);
+    const bool can_hier = hier_fits(I, gx, gy, d.n_poses, d.capacity);
+    if (a.tile_sort == HS_TILE_SORT_RADIX) c->tile_sort = kTileSortRadix;
+    else if (a.tile_sort == HS_TILE_SORT_HIER && can_hier) c->tile_sort = kTileSortHier;
+    else if (a.tile_sort == HS_TILE_SORT_COUNT) c->tile_sort = can_count ? kTileSortCount : kTileSortRadix;
+    else if (can_count) c->tile_sort = kTileSortCount;
+    else c->tile_sort = (HS_TUNE_HIER_DEFAULT && can_hier) ? kTileSortHier : kTileSortRadix;
+    if (!depth_msd_fits(I) || a.depth_sort == HS_DEPTH_SORT_PASSES) c->depth_sort = kDepthSortLsd;
+    else if (a.depth_sort == HS_DEPTH_SORT_COUNT) c->depth_sort = kDepthSortMsd;
+    else {
+        const int v = g_depth_sort.load(std::memory_order_relaxed);
+        c->depth_sort = v >= 0 ? v : (HS_TUNE_DEPTH_MSD_DEFAULT ? kDepthSortMsd : kDepthSortLsd);
+    }
+    c->tickets = a.chain_order ? a.chain_order == HS_CHAIN_TICKETS : g_sort_tickets.load(std::memory_order_relaxed) != 0;
+    // (the scan inside the emission is a blockIdx-ordered look-back chain like the radix passes': once the process has gone
+    // to ticket order -- a chain stalled, several processes share the GPU -- the offsets come from the three kernels ahead
+    // of the emission, which wait for nobody)
+    c->scan_in_emission = a.emission_scan ? a.emission_scan == HS_EMISSION_SCAN_INSIDE : (I >= (2 << 20) && !c->tickets);
+    c->range_cap = a.depth_range_cap == 0 ? kMsdCap : (a.depth_range_cap < 64 ? 64 : (a.depth_range_cap > kMsdCap ? kMsdCap : a.depth_range_cap));
+    c->dist_max = a.depth_dist_max == 0 ? 16 : (a.depth_dist_max < 0 ? 0 : (a.depth_dist_max > 16 ? 16 : a.depth_dist_max));
+    return HS_OK;
+}
 
 // Stamp of a single-enqueue forward (hs_common.h, kDepthBitsAt): never 0, never the same for two calls of a process that
 // could meet in the same memory (2^32 - 1 calls apart).  The only thing the library counts.
@@ -266,6 +252,8 @@ int hs_forward(const hs_fwd_args* a, void* hip_stream) {
     int rc = plan(a->dims, &sz, &L);
     if (rc) return rc;
     if ((rc = check_flags(a->flags, "hs_forward"))) return rc;
+    SortChoice sort;
+    if ((rc = resolve_sorts(*a, &sort))) return rc;
     if (a->dims.P > 0) {  // an empty cloud has no arrays to validate: it renders the background
         rc = check_common(a->dims, a->means3D, a->shs, a->colors_precomp, a->scales, a->rotations, a->cov3D_precomp,
                           a->viewmatrices, a->projmatrices, a->camposes, a->bg, "hs_forward");
@@ -311,7 +299,7 @@ int hs_forward(const hs_fwd_args* a, void* hip_stream) {
     if ((a->stages & HS_STAGE_BIN) && !(a->stages & HS_STAGE_PREPROCESS_ONLY)) {
         if (!a->binning) { set_error("hs_forward: null binning workspace"); return HS_EINVAL; }
         if (a->dims.P > 0) {
-            rc = launch_binning(*a, L, s, frame_tag);
+            rc = launch_binning(*a, L, sort, s, frame_tag);
             if (rc) return rc;
             if ((rc = debug_sync(a->flags, s, "binning"))) return rc;
         }   // (an empty cloud: launch_empty_frame above cleared the ranges and wrote the host copy of the counters)
@@ -406,8 +394,8 @@ int hs_depth_sort(int mode) {
 }
 
 int hs_sort_tickets(int enable) {
-    if (enable >= 0) { (void)hs::sort_tickets(); hs::g_sort_tickets.store(enable ? 1 : 0, std::memory_order_relaxed); }
-    return hs::sort_tickets() ? 1 : 0;
+    if (enable >= 0) hs::g_sort_tickets.store(enable ? 1 : 0, std::memory_order_relaxed);
+    return hs::g_sort_tickets.load(std::memory_order_relaxed);
 }
 
 int hs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, uint8_t* visible, void* hip_stream) {

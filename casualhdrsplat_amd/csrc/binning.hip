@@ -189,7 +189,7 @@ __device__ __forceinline__ uint32_t digit_of(K k, int shift, uint32_t mask) {
 //     (they depend on the pass' input alone), publishes them by compare-and-swap and walks on (see the look-back): no wait
 //     depends on a block that has not started, the chain advances under any dispatch order.  Helps are counted in
 //     fail_word[5] (hs_counters.reserved[4]); the host takes them as the sign of a shared GPU and moves to ticket order;
-//   * HS_SORT_TICKETS=1 in the environment (or hs_sort_tickets(1)) selects the TICKET instantiation, in which a block's
+//   * hs_fwd_args.chain_order = HS_CHAIN_TICKETS (or hs_sort_tickets(1)) selects the TICKET instantiation, in which a block's
 //     chain position is a ticket drawn from a per-pass counter when it STARTS (one atomic per block): position p < b then
 //     means block p is already running, nobody ever waits for an unstarted block, nothing needs help -- the faster mode on
 //     a shared GPU.  Alone it costs +30 us per frame at c3 (six passes of one same-address atomic per block), which is
@@ -606,7 +606,7 @@ struct SortScratch {
 template <int ITEMS, int LOOK>
 int radix_sort_packed(uint2* p0, uint2* p1, uint32_t* keys_out, uint32_t* vals_out, const uint32_t* n_dev, int64_t n_launch,
                       int nbits, void* tmp, uint32_t* fail_word, uint32_t* kill_word, hipStream_t s, bool zeroed,
-                      bool ghist_ready) {
+                      bool ghist_ready, bool tickets) {
     if (n_launch <= 0) return HS_OK;
     constexpr int TILE = ITEMS * kSortBlock;
     const int nblk = ceil_div(n_launch, TILE);
@@ -628,7 +628,7 @@ int radix_sort_packed(uint2* p0, uint2* p1, uint32_t* keys_out, uint32_t* vals_o
     radix_sweep_kernel<uint32_t, ITEMS, LOOK, true, PO, TK><<<nblk, kSortBlock, 0, s>>>(                                 \
         in, nullptr, last ? (void*)keys_out : (void*)out, last ? vals_out : nullptr, n_dev, shift, mask, st, gh, tk,  \
         fail_word, kill_word)
-        if (sort_tickets()) { if (last) HS_SWEEP(false, true); else HS_SWEEP(true, true); }
+        if (tickets) { if (last) HS_SWEEP(false, true); else HS_SWEEP(true, true); }
         else { if (last) HS_SWEEP(false, false); else HS_SWEEP(true, false); }
 #undef HS_SWEEP
         HS_LAUNCH_CHECK();
@@ -1254,7 +1254,7 @@ __global__ void __launch_bounds__(256) gather_binfo_kernel(int64_t I, const uint
 //   * inside it: the emission gathers its rectangles itself and learns the earlier blocks' pairs by decoupled look-back
 //     -- c3 0.229 (the chain over 3906 blocks costs more than two tiny kernels), c4 1.581 (three passes over 8 M
 //     instances and 130 MB of intermediate arrays less), c2 0.111.
-// (the switch: scan_in_emission(I), api.hip -- from 2^21 instances on; HS_SCAN_IN_EMISSION=0/1 forces it)
+// (the switch: SortChoice.scan_in_emission, api.hip -- from 2^21 instances on; hs_fwd_args.emission_scan forces it)
 constexpr uint64_t kScFlag = 3ull << 62, kScAgg = 1ull << 62, kScIncl = 2ull << 62, kScPoison = 3ull << 62;
 __device__ __forceinline__ void sc_publish(uint64_t* p, uint64_t v) {
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2286,7 +2286,7 @@ int launch_tile_keys(const hs_fwd_args& a, const hs_layout& L, hipStream_t s) {
     return HS_OK;
 }
 
-int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint32_t frame_tag) {
+int launch_binning(const hs_fwd_args& a, const hs_layout& L, const SortChoice& sort, hipStream_t s, uint32_t frame_tag) {
     const hs_dims& d = a.dims;
     char* geom = (char*)a.geom;
     char* bin = (char*)a.binning;
@@ -2316,7 +2316,7 @@ int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint
                                                 (uint32_t*)scan_status, pair_scratch_words(I, d.capacity, passes));
     }
 
-    if (fault_injection() == 2 && !sort_tickets())   // tests only (HS_FAULT_INJECT=stalled_chain): the verdict of a stalled chain
+    if (fault_injection() == 2 && !sort.tickets)   // tests only (HS_FAULT_INJECT=stalled_chain): the verdict of a stalled chain
         HS_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)&counters->overflow, 2, 1, s));
     // 1. instances by depth: stable, over the bits of the depth keys that VARY, in digits of up to nine bits (three passes
     //    for a scene spanning up to 2^4 in depth; the layout lives on the device, so four passes are enqueued and those
@@ -2327,13 +2327,13 @@ int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint
     if (!prepared)
         depth_keys_kernel<<<ceil_div(I, 1024), 256, 0, s>>>(I, (const float*)(geom + L.depth), (const int*)(geom + L.radii), dp0,
                                                             depth_bits);
-    const int mode = tile_sort_mode(I, gx, gy, d.n_poses, d.capacity);
+    const int mode = sort.tile_sort;
     const int eblk = ceil_div(I, 256);
     // The rectangles in depth order and the sums per 256 instances of that order, which the emission's offsets come from:
     // written by the counting depth sort's last kernel on its way out, else by gather_binfo_kernel / hier_gather_kernel
     bool gathered = false;
     uint32_t* bsum = (uint32_t*)(dp0 + I);   // (= dp1: free once the depth sort is done)
-    if (depth_sort_mode(I) == kDepthSortMsd) {
+    if (sort.depth_sort == kDepthSortMsd) {
         // frames below 2^21 instances: one stable counting pass over the top varying bits + range sorts in LDS (kernels above)
         const int rows = (int)depth_msd_rows(I);
         uint32_t* dw = (uint32_t*)(bin + L.depth_ws);
@@ -2343,12 +2343,12 @@ int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint
         uint32_t* culled_rows = totals + kMsdBuckets;                       // [rows]
         depth_msd_count_kernel<4><<<rows, depth_msd_tile(I) / 4, 0, s>>>(dp0, n_inst, depth_bits, dtag, counts2, culled_rows);
         depth_msd_colscan_kernel<<<kMsdBuckets / 32, 1024, 0, s>>>(counts2, rows, (uint2*)bases, (uint2*)totals);
-        // the emission of a frame this size takes its rectangles gathered (unless HS_SCAN_IN_EMISSION=1 asks it to gather
+        // the emission of a frame this size takes its rectangles gathered (unless hs_fwd_args.emission_scan asks it to gather
         // them itself): the range sort does that on its way out, the block sums live in the count rows (dead by then)
         GatherOut G = {nullptr, nullptr, nullptr, nullptr, (uint32_t)I};
         uint32_t* zero_b = nullptr;
         int64_t n_zero_b = 0;
-        if (HS_TUNE_FUSE_GATHER && (mode == kTileSortHier || !scan_in_emission(I))) {
+        if (HS_TUNE_FUSE_GATHER && (mode == kTileSortHier || !sort.scan_in_emission)) {
             gathered = true;
             bsum = counts2;
             G.binfo = (const uint2*)(geom + L.binfo); G.srect = dp0; G.bsum = bsum;
@@ -2367,8 +2367,8 @@ int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint
                                                                   bsum, n_zero_a, zero_b, n_zero_b);
         const int range = depth_msd_range(I);
         depth_range_sort_kernel<<<ceil_div(I, range) + 1, kRangeThreads, 0, s>>>(dp1, dp0, depth_bits, dtag, totals, inst_sorted,
-                                                                                 counters, depth_range_cap(),
-                                                                                 max(1, tile_bits((uint32_t)(I - 1))), depth_dist_max(), G, range);
+                                                                                 counters, sort.range_cap,
+                                                                                 max(1, tile_bits((uint32_t)(I - 1))), sort.dist_max, G, range);
         HS_LAUNCH_CHECK();
     } else {
         const int nblk = ceil_div(I, kDepthTile);
@@ -2376,7 +2376,7 @@ int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint
         const uint32_t late = fault_injection() == 3 ? 0x80000000u : 0u;
         for (int pass = 0; pass < 4; ++pass) {
             uint32_t* st = dsc.status + (int64_t)pass * dsc.pass_words;
-            if (sort_tickets())
+            if (sort.tickets)
                 radix_sweep_kernel<uint32_t, kDepthSortItems, kDepthSortLook, true, true, true, kDepthBins, true>
                     <<<nblk, kDepthBins, 0, s>>>(dp0, nullptr, dp1, inst_sorted, n_inst, 0, late, st, dsc.ghist, dsc.tickets + pass,
                                                  &counters->overflow, nullptr, depth_bits, pass, dtag);
@@ -2437,7 +2437,7 @@ int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint
                 w = (kb - shift + (cpasses - pass) - 1) / (cpasses - pass);
                 uint32_t* st = sc.status + (int64_t)pass * sc.pass_words;
                 const uint32_t mask = ((1u << w) - 1u) | (fault_injection() == 3 ? 0x80000000u : 0u);
-                if (sort_tickets())
+                if (sort.tickets)
                     radix_sweep_kernel<uint32_t, kPairSortItems, kPairSortLook, true, true, true><<<nblk, kSortBlock, 0, s>>>(
                         in, nullptr, out, nullptr, hw, shift, mask, st, sc.ghist + 256 * pass, sc.tickets + pass,
                         &counters->overflow, hw);
@@ -2477,7 +2477,7 @@ int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint
     uint2* srect = nullptr;
     uint32_t* block_excl = nullptr;
     bool excl_ready = false;
-    if (!scan_in_emission(I)) {
+    if (!sort.scan_in_emission) {
         srect = dp0;
         block_excl = bsum;
         if (!gathered)
@@ -2508,7 +2508,7 @@ int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint
     uint32_t* keys_sorted = (uint32_t*)(bin + L.keys_sorted);
     int rc = radix_sort_packed<kPairSortItems, kPairSortLook>(p0, p1, keys_sorted, (uint32_t*)(bin + L.point_list), n_sort,
                                                          d.capacity, tbits, tmp2, &counters->overflow, n_sort, s,
-                                                         /*zeroed=*/true, /*ghist_ready=*/true);
+                                                         /*zeroed=*/true, /*ghist_ready=*/true, sort.tickets);
     if (rc != HS_OK) return rc;
     if (d.capacity > 0) {
         tile_ranges_kernel<<<ceil_div(d.capacity, 1024), 256, 0, s>>>(keys_sorted, n_sort, ranges, counters,

@@ -79,7 +79,9 @@ static inline int tile_bits(uint32_t n) {
 int launch_preprocess_fwd(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint32_t frame_tag);
 int launch_scan(const hs_fwd_args& a, const hs_layout& L, hipStream_t s);
 int launch_cov3d(const hs_fwd_args& a, const hs_layout& L, hipStream_t s);   // inspection: fills hs_layout.cov3D
-int launch_binning(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, uint32_t frame_tag);
+// `sort`: which sorts this forward runs (SortChoice below: resolved once per hs_forward, api.hip)
+struct SortChoice;
+int launch_binning(const hs_fwd_args& a, const hs_layout& L, const SortChoice& sort, hipStream_t s, uint32_t frame_tag);
 // an empty cloud (P == 0): cleared counters (when given), cleared tile ranges (when given), the host copy of the counters
 int launch_empty_frame(hs_counters* clear, uint2* ranges, int64_t ntiles, uint32_t* counters_host, const hs_counters* counters,
                        hipStream_t s);
@@ -149,13 +151,9 @@ static inline int64_t depth_msd_rows(int64_t I) { return (I + depth_msd_tile(I) 
 static inline int64_t depth_ws_words(int64_t I) {
     return depth_msd_fits(I) ? depth_msd_rows(I) * (kMsdBuckets / 2 + kMsdBuckets + 1) + kMsdBuckets : 0;   // (+ culled per row)
 }
-// Which depth sort a forward runs: HS_DEPTH_SORT=lsd / msd in the environment forces a form (read at every forward), else
-// hs_depth_sort()'s process-wide setting (the host moves it to the passes when a frame's ranges did not fit the LDS), else
-// the counting form wherever it fits.
+// Which depth sort a forward runs: hs_fwd_args.depth_sort forces a form, else hs_depth_sort()'s process-wide setting (the
+// host moves it to the passes when a frame's ranges did not fit the LDS), else the counting form -- wherever it fits.
 enum DepthSort { kDepthSortLsd = 0, kDepthSortMsd = 1 };
-int depth_sort_mode(int64_t I);
-int depth_range_cap();   // elements a range-sort workgroup keeps in LDS (kMsdCap; HS_DEPTH_RANGE_CAP lowers it: tests)
-int depth_dist_max();    // members of a bucket up to which a range is sorted by distribution (16; HS_DEPTH_DIST_MAX lowers it: tests)
 // Scratch behind hs_layout.pair_sort_tmp: one 64-bit status word per 256-instance block of the pair emission's chained scan
 // (as u32 words), then the pair sort's scratch.  pair_scratch_words = what must be cleared before the emission runs.
 static inline int64_t emit_scan_words(int64_t I) { return 2 * ((I + 255) / 256 + 2) / 64 * 64 + 64; }
@@ -178,17 +176,11 @@ int fault_injection();
 #else
 constexpr int fault_injection() { return 0; }
 #endif
-// HS_SORT_TICKETS=1 in the environment (read once): the pipeline's radix passes take their chain positions from tickets
-// instead of blockIdx (binning.hip, "Progress").
-bool sort_tickets();
-// Whether the pair emission computes its block offsets itself (chained scan) for a frame of I instances: from 2^21
-// instances on; HS_SCAN_IN_EMISSION=1 / 0 in the environment forces it on / off (tests run both paths at small sizes).
-bool scan_in_emission(int64_t I);
 static inline int sort_passes(int nbits) { return (nbits + 7) / 8; }
 // Tile sort of a small frame by counting instead of radix passes (binning.hip): the dims qualify when the (pose, tile) keys
 // fit the per-workgroup tables and the (emission workgroup x key) matrices stay small; the binning workspace then carries
-// the matrices (hs_layout.tile_matrix: counts | bases | totals).  HS_TILE_SORT=radix in the environment keeps the radix
-// passes (tests run both paths; read at every forward).
+// the matrices (hs_layout.tile_matrix: counts | bases | totals).  hs_fwd_args.tile_sort = HS_TILE_SORT_RADIX keeps the
+// radix passes (tests run both paths).
 constexpr int kCountTilesMax = 4096;
 constexpr int64_t kCountMatrixMax = 1ll << 21;
 static inline bool count_sort_fits(int64_t I, int64_t vtiles, int64_t capacity) {
@@ -243,11 +235,23 @@ struct HierWs {
 static inline int64_t hier_ws_words(int64_t I, int64_t gx, int64_t gy, int64_t n_poses, int64_t capacity) {
     return hier_fits(I, gx, gy, n_poses, capacity) ? HierWs(gx, gy, n_poses, capacity).words : 0;
 }
-// Which tile sort a forward of these dims runs: HS_TILE_SORT=radix / count / hier in the environment forces a form where
-// the dims allow it (read at every forward: the test suite switches it inside one process); recorded in
-// hs_counters.reserved[5] by the binning stage so that later inspection calls need not ask the environment again.
+// Which tile sort a forward of these dims runs: hs_fwd_args.tile_sort forces a form where the dims allow it; recorded in
+// hs_counters.reserved[5] by the binning stage so that later inspection calls can tell what the frame had.
 enum TileSort { kTileSortRadix = 0, kTileSortCount = 1, kTileSortHier = 2 };
-int tile_sort_mode(int64_t I, int64_t gx, int64_t gy, int64_t n_poses, int64_t capacity);
+// The sorts of ONE forward.  hs_forward resolves the sort fields of its hs_fwd_args and the process defaults (hs_depth_sort,
+// hs_sort_tickets) into this once, before anything is enqueued, and the binning stage takes it as a value: every kernel of a
+// frame is chosen under the same answers, whatever another thread sets meanwhile.  (The variables HS_TILE_SORT,
+// HS_DEPTH_SORT, HS_SORT_TICKETS, HS_SCAN_IN_EMISSION, HS_DEPTH_RANGE_CAP, HS_DEPTH_DIST_MAX are read by the Python host,
+// which fills the fields from them; the library reads no environment.)
+struct SortChoice {
+    int tile_sort;           // TileSort
+    int depth_sort;          // DepthSort
+    bool tickets;            // chain positions of the radix passes from tickets instead of blockIdx (binning.hip, "Progress")
+    bool scan_in_emission;   // the pair emission computes its block offsets itself (chained scan): by default from 2^21
+                             // instances on, unless the passes are ticket-ordered
+    int range_cap;           // elements a range-sort workgroup of the counting depth sort keeps in LDS (kMsdCap; tests lower it)
+    int dist_max;            // members of a bucket up to which such a range is sorted by distribution (16; tests lower it)
+};
 // keys_sorted of a frame whose pairs were sorted by counting, from its tile ranges (inspection: HS_STAGE_OFFSETS)
 int launch_tile_keys(const hs_fwd_args& a, const hs_layout& L, hipStream_t s);
 

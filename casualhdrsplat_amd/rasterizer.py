@@ -174,7 +174,7 @@ class _Pending:
     until someone asks."""
     def __init__(self, host, event, capacity, ticket_order=0):
         self.host, self.event, self.capacity = host, event, capacity
-        self.ticket_order = ticket_order   # chain-position mode the frame was ENQUEUED under (hs_sort_tickets(-1) then)
+        self.ticket_order = ticket_order   # chain-position mode the frame was ENQUEUED under (hs_fwd_args.chain_order)
 
     def resolve(self):
         """(num_rendered, overflowed) -- waits for the forward's counter copy on first use."""
@@ -231,7 +231,6 @@ class _Pending:
 
 def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, shs, colors_precomp, scales,
                  rotations, cov3D_precomp, exposure, crf_table, capacity: Optional[int], want_invdepth: bool = False):
-    lib = L.load()
     dev = means3D.device
     if dev.type != "cuda":
         raise RuntimeError("casualhdrsplat_amd rasterizes on an MI355X only: tensors must live on a cuda (HIP) device")
@@ -299,11 +298,10 @@ def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, sh
     st = _State()
     st.pending = None
     stream = _stream()
-    ticket_order = lib.hs_sort_tickets(-1)   # the chain-position mode this frame's passes are enqueued under
     if sync_mode:
         # upstream semantics: one host read of num_rendered between the scan and the binning
         a.stages = L.HS_STAGE_PREPROCESS
-        L.check(lib.hs_forward(C.byref(a), stream), "hs_forward[preprocess]")
+        L.forward(a, stream, "hs_forward[preprocess]")
         R = int(geom[:4].view(torch.int32).item()) & 0xFFFFFFFF if P > 0 else 0
         dims, sizes, layout = L.plan(P, M, int(settings.sh_degree), W, H, N, R, crf_K)
         a.dims = dims
@@ -322,7 +320,7 @@ def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, sh
                            "does that): page-locked memory cannot be allocated while a stream is capturing")
     host = _PINNED_POOL.pop() if _PINNED_POOL else torch.empty(8, dtype=torch.int32).pin_memory()
     a.counters_host = host.data_ptr()
-    L.check(lib.hs_forward(C.byref(a), stream), "hs_forward")
+    ticket_order = L.forward(a, stream, "hs_forward")   # the chain-position mode this frame's passes are enqueued under
     a.counters_host = None   # (the saved argument struct may be replayed by profiling helpers: never into a recycled buffer)
     ev = torch.cuda.Event()
     ev.record()
@@ -662,7 +660,7 @@ def replay_forward(out_tensor: torch.Tensor, stages: int = L.HS_STAGE_RENDER) ->
     scratch_hdr = torch.empty_like(out_tensor) if (st.flags & L.HS_FLAG_HDR) else None
     scratch_radii = torch.empty(max(st.dims.P, 1), dtype=torch.int32, device=out_tensor.device)
     a.out_hdr, a.radii, a.out_invdepth = _ptr(scratch_hdr), scratch_radii.data_ptr(), None
-    L.check(L.load().hs_forward(C.byref(a), _stream()), "hs_forward[replay]")
+    L.forward(a, _stream(), "hs_forward[replay]")
     a.out_hdr, a.radii = None, None  # scratch dies with this call
 
 
@@ -915,7 +913,7 @@ def inspect_state(out_tensor) -> dict:
     if I > 0:  # instance-order offsets (a5 as published) are not part of the forward: fill them now
         a = st.fwd_args
         a.stages = L.HS_STAGE_OFFSETS
-        L.check(L.load().hs_forward(C.byref(a), _stream()), "hs_forward[offsets]")
+        L.forward(a, _stream(), "hs_forward[offsets]")
     rec = view(st.geom, lay.rec, I * 16, torch.float32).reshape(I, 16)
     depths = view(st.geom, lay.depth, I, torch.float32)
     tile_sorted = view(st.binning, lay.keys_sorted, R, torch.int32).to(torch.int64) & 0xFFFFFFFF

@@ -35,7 +35,8 @@ extern "C" {
 /* libhdrsplat.so is built with -fvisibility=hidden: the hs_* entry points below are its only exported symbols */
 #define HS_API __attribute__((visibility("default")))
 
-#define HS_VERSION 308
+#define HS_VERSION 309 /* 309: hs_fwd_args grew the sort selection fields (tile_sort ... depth_dist_max) at its end; the
+                          library reads no environment variable any more */
 
 #define HS_OK 0
 #define HS_EINVAL (-1)    /* bad argument (null pointer, bad shape, unsupported degree ...) */
@@ -69,6 +70,17 @@ extern "C" {
  * start that exchange between them) */
 #define HS_BWD_SEGSUM 8      /* per-instance record sums (+ dL_dview_colors when given) */
 #define HS_BWD_PROJECT 16    /* computeCov2D/projection/SH/cov3D backward from the record sums */
+
+/* (HS_VERSION 309) hs_fwd_args.tile_sort / depth_sort / chain_order / emission_scan: 0 = auto in each */
+#define HS_TILE_SORT_RADIX 1   /* stable look-back radix passes over the tile ids */
+#define HS_TILE_SORT_COUNT 2   /* counting sort (small frames: hs_layout.tile_matrix); radix passes where it does not fit */
+#define HS_TILE_SORT_HIER 3    /* hierarchical (hs_layout.hier_ws); the automatic choice where it does not fit */
+#define HS_DEPTH_SORT_PASSES 1 /* stable look-back radix passes */
+#define HS_DEPTH_SORT_COUNT 2  /* counting pass + range sorts (hs_depth_sort); look-back passes from 2^21 instances on */
+#define HS_CHAIN_BLOCKIDX 1    /* chain positions of the radix passes: blockIdx ... */
+#define HS_CHAIN_TICKETS 2     /* ... or tickets drawn when a block starts (hs_sort_tickets) */
+#define HS_EMISSION_SCAN_AHEAD 1  /* slot offsets of the pair emission from kernels of their own ahead of it ... */
+#define HS_EMISSION_SCAN_INSIDE 2 /* ... or from a chained scan inside its launch */
 
 /* flags */
 #define HS_FLAG_HDR 1          /* exposure * CRF tone-map epilogue; out_color = LDR, out_hdr = radiance */
@@ -150,6 +162,24 @@ typedef struct hs_fwd_args {
                                     hipHostMalloc / torch pin_memory return): HS_STAGE_BIN leaves a copy of hs_counters
                                     (32 bytes) there -- written by its last kernel, so a sync-free caller that wants to
                                     look at num_rendered / overflow LATER needs no copy of its own on the stream */
+    /* (HS_VERSION 309) Which sorts HS_STAGE_BIN runs for THIS call.  All zero (a zero-initialised struct) = the library's
+     * own choice, as before; the result is the same bit for bit whichever form runs (a stable sort has one result), so
+     * these select speed and code path only.  hs_forward resolves them once, before it enqueues anything, together with
+     * the process defaults of hs_depth_sort / hs_sort_tickets: two callers in one process may run different sorts, and
+     * no kernel of a frame is chosen under other answers than the rest.  A value outside an enumeration is HS_EINVAL.
+     * The library reads no environment variable: the Python host fills these fields from HS_TILE_SORT, HS_DEPTH_SORT,
+     * HS_SCAN_IN_EMISSION, HS_DEPTH_RANGE_CAP and HS_DEPTH_DIST_MAX at every call (casualhdrsplat_amd/_lib.py). */
+    int32_t tile_sort;       /* 0 = auto: counting where it fits (hs_layout.tile_matrix), else hierarchical where that fits
+                                (hs_layout.hier_ws), else radix passes; or HS_TILE_SORT_*.  A forced form that does not
+                                fit the dims falls back as noted there; hs_counters.reserved[5] tells what ran */
+    int32_t depth_sort;      /* 0 = auto: hs_depth_sort()'s process-wide setting; or HS_DEPTH_SORT_* */
+    int32_t chain_order;     /* 0 = auto: hs_sort_tickets()'s process-wide setting; or HS_CHAIN_* */
+    int32_t emission_scan;   /* 0 = auto: inside the emission from 2^21 instances on unless the chain order is tickets,
+                                ahead of it otherwise; or HS_EMISSION_SCAN_* */
+    int32_t depth_range_cap; /* tests: elements a range-sort workgroup of the counting depth sort keeps in its LDS before
+                                it goes through memory; 0 = 4096 (all that fit), else clamped to [64, 4096]; < 0 invalid */
+    int32_t depth_dist_max;  /* tests: members of a bucket up to which such a range is sorted by distribution; 0 = 16 (the
+                                default), -1 = none (every range by digit passes), else clamped to at most 16 */
 } hs_fwd_args;
 
 typedef struct hs_bwd_args {
@@ -228,7 +258,11 @@ typedef struct hs_layout {
      * depth_pairs = scratch of the depth sort (2 x I 8-byte (depth bits, instance) elements), inst_sorted = the
      * instances in depth order (u32 x I), offs_sorted = inclusive scan of their pair counts in that order (u32 x I:
      * instance inst_sorted[i] owns the pair slots [offs_sorted[i-1], offs_sorted[i])); sort_tmp / pair_sort_tmp = scratch
-     * of the depth sort / of the pair emission's scan and the tile sort (digit totals, status words) */
+     * of the depth sort / of the pair emission's scan and the tile sort (digit totals, status words).
+     * keys_sorted is written by the RADIX tile sort only (its last pass; tile_ranges reads it).  The counting and the
+     * hierarchical tile sort write point_list and ranges and leave keys_sorted alone (nothing in the pipeline reads it):
+     * after such a frame it holds scratch until an HS_STAGE_OFFSETS call rebuilds it from the ranges for inspection.
+     * hs_counters.reserved[5] tells which tile sort a frame had (0 radix, 1 counting, 2 hierarchical). */
     int64_t keys_sorted, point_list, pairs_tmp, ranges, sort_tmp, depth_pairs, inst_sorted, offs_sorted, pair_sort_tmp;
     /* pair_flags (binning workspace): u8 per pair slot, cleared by the forward's pair emission, set to 1 by the
      * render backward for the records it wrote */
@@ -250,13 +284,13 @@ typedef struct hs_layout {
     /* (HS_VERSION 305) tile_matrix (binning workspace; empty unless the frame is small: <= 4096 (pose, tile) keys and
      * <= 2^21 (emission workgroup, key) entries): scratch of the counting tile sort such frames get instead of radix passes
      * -- u32 [ceil(I/256)][keys] pair counts (one byte per wave) | u32 [ceil(I/256)][keys] pairs of the key in earlier
-     * workgroups | u32 [keys] totals.  Such a forward writes point_list and ranges but NOT keys_sorted (nothing reads it);
-     * HS_STAGE_OFFSETS fills keys_sorted from the ranges for inspection. */
+     * workgroups | u32 [keys] totals.  Such a forward writes point_list and ranges but NOT keys_sorted (see there). */
     int64_t tile_matrix;
     /* (HS_VERSION 307) hier_ws (binning workspace; empty unless the frame has <= 2048 (pose, 8 x 8-tile super-tile) keys):
      * scratch of the hierarchical tile sort -- u32 header | element counts per super-tile | pairs per tile | first sorted
-     * position per tile | first element / chunk per super-tile | chunk descriptors | per-chunk pair counts.  Selected with
-     * HS_TILE_SORT=hier in the environment; like the counting sort it writes point_list and ranges but not keys_sorted.
+     * position per tile | first element / chunk per super-tile | chunk descriptors | per-chunk pair counts.  The default
+     * for frames the counting sort does not take and that have <= 2048 (pose, super-tile) keys (hs_fwd_args.tile_sort
+     * forces it on smaller ones); like the counting sort it writes point_list and ranges but not keys_sorted.
      * hs_counters.reserved[5] records which tile sort a forward ran (0 radix, 1 counting, 2 hierarchical). */
     int64_t hier_ws;
     /* (HS_VERSION 308) depth_ws (binning workspace; empty unless the frame has fewer than 2^21 instances): scratch of the
@@ -320,8 +354,8 @@ HS_API int hs_render_stats(const hs_fwd_args* fwd /* or NULL */, const hs_bwd_ar
  * depth sliver of 1 / 4096 of the key range holds more than ~2048 instances; a range that does is sorted through memory by
  * its one workgroup -- correct, but a frame dominated by such a range (a wall of Gaussians at one depth seen head-on)
  * is slower than with the passes.  hs_counters.reserved[2] counts those ranges; the Python host moves the process to 0
- * when a frame reports any.  mode < 0 only queries.  Returns the setting in force.  HS_DEPTH_SORT=lsd / msd in the
- * environment overrides it per forward. */
+ * when a frame reports any.  mode < 0 only queries.  Returns the setting in force.  hs_fwd_args.depth_sort overrides
+ * it per forward. */
 HS_API int hs_depth_sort(int mode);
 
 /* Chain positions of the radix passes of HS_STAGE_BIN, process-wide: 0 = blockIdx (default: relies on every XCD handing
@@ -331,9 +365,10 @@ HS_API int hs_depth_sort(int mode);
  * process' waiting blocks keep out; a waiting block then computes the silent predecessor's counts itself -- correct,
  * counted in hs_counters.reserved[4], but slower than never having to).
  * With 1 the pair emission also takes its slot offsets from kernels of their own instead of its in-launch chain.
- * enable < 0 only queries.  Returns the setting in force.  Initial value: HS_SORT_TICKETS=1 in the environment, else 0.
- * The Python host switches to 1 by itself once frames report helps (or, should a pass ever give up: overflow = 2, after
- * which it asks for the step again). */
+ * enable < 0 only queries.  Returns the setting in force.  Initial value: 0; hs_fwd_args.chain_order overrides it per
+ * forward.  The Python host calls hs_sort_tickets(1) when it loads the library with HS_SORT_TICKETS=1 in the environment,
+ * and switches to 1 by itself once frames report helps (or, should a pass ever give up: overflow = 2, after which it asks
+ * for the step again). */
 HS_API int hs_sort_tickets(int enable);
 
 /* (HS_VERSION 308, detected by name) Photometric training loss of the published 3DGS train.py, fused (loss.hip):

@@ -52,6 +52,25 @@ static int run() {
     std::memset(&f, 0, sizeof f);
     f.dims = hs_dims{10, 1, 0, 32, 32, 1, 100, 0, 0};
     CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "null"));
+    // (HS_VERSION 309) the sort selection of a call: all zero = the library's choice (above); a value outside its
+    // enumeration is refused with the fields in the message, every value inside passes on to the next check
+    f.tile_sort = HS_TILE_SORT_HIER + 1;
+    CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "tile_sort=4"));
+    f.tile_sort = -1;
+    CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "sort selection"));
+    f.tile_sort = HS_TILE_SORT_HIER; f.depth_sort = HS_DEPTH_SORT_COUNT + 1;
+    CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "depth_sort=3"));
+    f.depth_sort = HS_DEPTH_SORT_COUNT; f.chain_order = HS_CHAIN_TICKETS + 1;
+    CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "chain_order=3"));
+    f.chain_order = HS_CHAIN_TICKETS; f.emission_scan = HS_EMISSION_SCAN_INSIDE + 1;
+    CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "emission_scan=3"));
+    f.emission_scan = HS_EMISSION_SCAN_INSIDE; f.depth_range_cap = -1;
+    CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "depth_range_cap=-1"));
+    f.depth_range_cap = 1 << 30; f.depth_dist_max = -2;
+    CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "depth_dist_max=-2"));
+    f.depth_dist_max = -1;
+    CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "null"));
+    f.tile_sort = f.depth_sort = f.chain_order = f.emission_scan = f.depth_range_cap = f.depth_dist_max = 0;
     float* fake = reinterpret_cast<float*>(4096);  // never dereferenced on the host
     f.means3D = f.viewmatrices = f.projmatrices = f.camposes = f.bg = f.shs = f.colors_precomp = f.scales = f.rotations = fake;
     CHECK(hs_forward(&f, nullptr) == HS_EINVAL && std::strstr(hs_last_error(), "exactly one"));

@@ -54,6 +54,17 @@ def test_fault_injection_exists_only_in_the_test_library(lib):
         assert re.search(rf"\bT {n}\b", out), n
 
 
+def test_the_library_reads_no_sort_switch_from_the_environment(lib):
+    """The sort selection travels in hs_fwd_args (HS_VERSION 309); the variables that used to carry it are the Python
+    host's concern (_lib.sort_options).  Neither build of the library contains their names: there is no getenv left to
+    race a putenv."""
+    for path in (lib.LIB_PATH, os.path.join(os.path.dirname(lib.LIB_PATH), "libhdrsplat_test.so")):
+        blob = open(path, "rb").read()
+        for name in (b"HS_TILE_SORT", b"HS_DEPTH_SORT", b"HS_SCAN_IN_EMISSION", b"HS_SORT_TICKETS", b"HS_DEPTH_RANGE_CAP",
+                     b"HS_DEPTH_DIST_MAX"):
+            assert name not in blob, (path, name)
+
+
 def test_struct_sizes_match_c(lib, tmp_path):
     """ctypes mirrors must have the layout the C compiler gives include/hdrsplat.h."""
     src = tmp_path / "sz.c"
@@ -70,7 +81,7 @@ def test_struct_sizes_match_c(lib, tmp_path):
 
 def test_version_and_plan(lib):
     L = lib.load()
-    assert L.hs_version() == 308
+    assert L.hs_version() == 309 == lib.HS_VERSION
     d, sz, lay = lib.plan(1_000_000, 16, 3, 1920, 1080, 1, 7_000_000)
     assert sz.geom_bytes > 1_000_000 * 48 and sz.binning_bytes > 7_000_000 * 16
     assert sz.image_bytes >= 1920 * 1080 * (8 + 12) and sz.bwd_bytes >= 7_000_000 * 48
@@ -196,6 +207,25 @@ def test_forward_backward_validate_before_touching_the_gpu(lib):
     assert L.hs_sort_pairs(None, None, None, None, 5, 40, None, None) == lib.HS_EINVAL
 
 
+def test_forward_rejects_sort_selections_outside_their_enumerations(lib):
+    """hs_fwd_args.tile_sort ... depth_dist_max (HS_VERSION 309): zero is "auto", a value outside a field's enumeration
+    is HS_EINVAL with the fields in the message -- before any pointer is looked at, before any HIP call."""
+    L = lib.load()
+    a = lib.hs_fwd_args()
+    a.dims = lib.hs_dims(10, 1, 0, 32, 32, 1, 100)
+    for field, bad in (("tile_sort", 4), ("tile_sort", -1), ("depth_sort", 3), ("chain_order", 3), ("emission_scan", 3),
+                       ("depth_range_cap", -1), ("depth_dist_max", -2)):
+        setattr(a, field, bad)
+        assert L.hs_forward(C.byref(a), None) == lib.HS_EINVAL
+        assert f"{field}={bad}".encode() in L.hs_last_error(), (field, L.hs_last_error())
+        setattr(a, field, 0)
+    # every value inside the enumerations passes on to the next check (the null pointers of this struct)
+    a.tile_sort, a.depth_sort, a.chain_order, a.emission_scan = (lib.HS_TILE_SORT_HIER, lib.HS_DEPTH_SORT_COUNT,
+                                                                 lib.HS_CHAIN_TICKETS, lib.HS_EMISSION_SCAN_INSIDE)
+    a.depth_range_cap, a.depth_dist_max = 1 << 30, -1
+    assert L.hs_forward(C.byref(a), None) == lib.HS_EINVAL and b"null" in L.hs_last_error()
+
+
 def test_sh_backward_views_validates_before_touching_the_gpu(lib):
     """hs_sh_backward_views (the local half of the view-parallel exchange): argument errors come back as HS_EINVAL."""
     L = lib.load()
@@ -225,3 +255,56 @@ def test_host_code_is_clean_under_address_and_ub_sanitizers():
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "asan_host: clean" in r.stdout and "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr
+
+
+def test_a_library_of_another_version_is_refused(lib, monkeypatch):
+    """load() compares hs_version() with the HS_VERSION its ctypes structs mirror: a stale build (a variant library picked
+    through HS_LIB_PATH) would read the grown hs_fwd_args short."""
+    monkeypatch.setattr(lib, "_lib", None)
+    monkeypatch.setattr(lib, "HS_VERSION", lib.HS_VERSION + 1)
+    with pytest.raises(RuntimeError, match=f"HS_VERSION {lib.HS_VERSION - 1}.*rebuild"):
+        lib.load()
+
+
+def test_sort_options_parse_the_environments_switches_as_the_library_used_to(lib):
+    """_lib.sort_options: the spellings in use (tests, scripts, bench.py, __graft_entry__.py) -> hs_fwd_args fields."""
+    auto = dict(tile_sort=0, depth_sort=0, emission_scan=0, depth_range_cap=0, depth_dist_max=0)
+    assert lib.sort_options({}) == auto
+    assert lib.sort_options({"HS_SORT_TICKETS": "1", "HS_GUARD": "1"}) == auto     # (tickets: a process default, see load())
+
+    def one(k, v):
+        got = lib.sort_options({k: v})
+        changed = {f: x for f, x in got.items() if x != auto[f]}
+        assert len(changed) <= 1
+        return changed
+    assert one("HS_TILE_SORT", "radix") == dict(tile_sort=lib.HS_TILE_SORT_RADIX) == dict(tile_sort=1)
+    assert one("HS_TILE_SORT", "count") == dict(tile_sort=lib.HS_TILE_SORT_COUNT) == dict(tile_sort=2)
+    assert one("HS_TILE_SORT", "hier") == dict(tile_sort=lib.HS_TILE_SORT_HIER) == dict(tile_sort=3)
+    assert one("HS_TILE_SORT", "h") == dict(tile_sort=3) and one("HS_TILE_SORT", "") == {} and one("HS_TILE_SORT", "auto") == {}
+    assert one("HS_DEPTH_SORT", "lsd") == dict(depth_sort=lib.HS_DEPTH_SORT_PASSES) == dict(depth_sort=1)
+    assert one("HS_DEPTH_SORT", "msd") == dict(depth_sort=lib.HS_DEPTH_SORT_COUNT) == dict(depth_sort=2)
+    assert one("HS_DEPTH_SORT", "") == {}
+    assert one("HS_SCAN_IN_EMISSION", "1") == dict(emission_scan=lib.HS_EMISSION_SCAN_INSIDE) == dict(emission_scan=2)
+    assert one("HS_SCAN_IN_EMISSION", "0") == dict(emission_scan=lib.HS_EMISSION_SCAN_AHEAD) == dict(emission_scan=1)
+    assert one("HS_SCAN_IN_EMISSION", "") == dict(emission_scan=1)      # set, not '1': forced off, as getenv + e[0] gave
+    # atoi + clamp: [64, 4096] elements; a set variable never maps to 0 (= not set)
+    assert one("HS_DEPTH_RANGE_CAP", "64") == dict(depth_range_cap=64) and one("HS_DEPTH_RANGE_CAP", "2000") == dict(depth_range_cap=2000)
+    assert one("HS_DEPTH_RANGE_CAP", "0") == dict(depth_range_cap=64) and one("HS_DEPTH_RANGE_CAP", "x") == dict(depth_range_cap=64)
+    assert one("HS_DEPTH_RANGE_CAP", "99999999999") == dict(depth_range_cap=4096)
+    # [0, 16] members; "0 members" is -1 in the field
+    assert one("HS_DEPTH_DIST_MAX", "0") == dict(depth_dist_max=-1) and one("HS_DEPTH_DIST_MAX", "-3") == dict(depth_dist_max=-1)
+    assert one("HS_DEPTH_DIST_MAX", "8") == dict(depth_dist_max=8) and one("HS_DEPTH_DIST_MAX", " 12abc") == dict(depth_dist_max=12)
+    assert one("HS_DEPTH_DIST_MAX", "16") == dict(depth_dist_max=16) and one("HS_DEPTH_DIST_MAX", "400") == dict(depth_dist_max=16)
+
+
+def test_sort_tickets_in_the_environment_set_the_process_default_when_the_library_loads(lib):
+    """HS_SORT_TICKETS=1 is applied once, by load() (hs_sort_tickets(1)); the library's own initial value is 0 whatever
+    the environment says.  In child processes: the setting is process-wide."""
+    import sys
+    code = ("import ctypes, sys; sys.path.insert(0, %r); from casualhdrsplat_amd import _lib; "
+            "raw = ctypes.CDLL(_lib.LIB_PATH); before = raw.hs_sort_tickets(-1); print(before, _lib.load().hs_sort_tickets(-1))" % ROOT)
+    for value, want in (("1", "0 1"), ("0", "0 0"), (None, "0 0")):
+        env = {k: v for k, v in os.environ.items() if k != "HS_SORT_TICKETS"}
+        if value is not None:
+            env["HS_SORT_TICKETS"] = value
+        assert subprocess.check_output([sys.executable, "-c", code], env=env, text=True).split("\n")[0] == want

@@ -127,6 +127,24 @@ def test_ldr_forward_backward_vs_oracle(oracle, P, W, H, deg, seed, cam_seed):
     Hh.assert_grads_bounded(g2, b2, what=f"P={P} masked")
 
 
+@contextlib.contextmanager
+def environment(**kv):
+    """os.environ[k] = v (None: k unset) for the forwards inside; what was there before comes back afterwards.  (The Python
+    host reads the sort switches at every forward and hands them to the library inside the call: _lib.sort_options.)"""
+    def put(d):
+        for k, v in d.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = str(v)
+    was = {k: os.environ.get(k) for k in kv}
+    put(kv)
+    try:
+        yield
+    finally:
+        put(was)
+
+
 @pytest.fixture(params=["default", "tickets", "scan_in_emission", "radix_tile_sort", "scan_in_emission+counting", "hier",
                         "hier+tickets", "lsd_depth_sort"])
 def binning_mode(request):
@@ -142,24 +160,20 @@ def binning_mode(request):
     LDS): the "tickets" forms and "lsd_depth_sort" keep the look-back passes of the depth sort on them."""
     from casualhdrsplat_amd import _lib as L
     lib = L.load()
-    was, env = lib.hs_sort_tickets(-1), {k: os.environ.get(k) for k in ("HS_SCAN_IN_EMISSION", "HS_TILE_SORT", "HS_DEPTH_SORT")}
+    was, env = lib.hs_sort_tickets(-1), {}
     if request.param in ("tickets", "hier+tickets", "lsd_depth_sort"):
-        os.environ["HS_DEPTH_SORT"] = "lsd"
+        env["HS_DEPTH_SORT"] = "lsd"
     if request.param in ("tickets", "hier+tickets"):
         lib.hs_sort_tickets(1)
     if request.param.startswith("hier"):   # round 6: coarse stable pass over (super-tile, instance) elements + expansion
-        os.environ["HS_TILE_SORT"] = "hier"
+        env["HS_TILE_SORT"] = "hier"
     if request.param.startswith("scan_in_emission"):
-        os.environ["HS_SCAN_IN_EMISSION"] = "1"
+        env["HS_SCAN_IN_EMISSION"] = "1"
     if request.param in ("tickets", "scan_in_emission", "radix_tile_sort"):
-        os.environ["HS_TILE_SORT"] = "radix"
-    yield request.param
+        env["HS_TILE_SORT"] = "radix"
+    with environment(**env):
+        yield request.param
     lib.hs_sort_tickets(was)
-    for k, v in env.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = v
 
 
 @pytest.mark.parametrize("case", ["ldr_20000", "tiles_14400", "c1_hdr_fixture"])
@@ -525,7 +539,7 @@ def test_overflow_in_a_training_step_raises_then_the_repeated_step_succeeds(form
     computed from an empty frame) and leaves the rasterizer with a capacity that fits, so repeating the step works
     and matches the synchronous path.  Through each of the three tile sorts (every one has its own verdict path: the pair
     emission's, the hierarchical emission's, the counting scatter's)."""
-    with tile_sort(form):
+    with environment(HS_TILE_SORT=form):
         _overflow_in_a_training_step()
 
 
@@ -628,18 +642,74 @@ def skewed_scene(P=30000, W=640, H=384, deg=1, seed=31):
     return sc
 
 
-@contextlib.contextmanager
-def tile_sort(form):
-    """HS_TILE_SORT=form for the forwards inside (read by the library at every forward)."""
-    was = os.environ.get("HS_TILE_SORT")
-    os.environ["HS_TILE_SORT"] = form
-    try:
-        yield
-    finally:
-        if was is None:
-            os.environ.pop("HS_TILE_SORT", None)
-        else:
-            os.environ["HS_TILE_SORT"] = was
+def test_sort_selection_travels_in_the_call_two_frames_of_one_process_run_different_sorts():
+    """hs_fwd_args.tile_sort / depth_sort / chain_order (HS_VERSION 309): the same small frame enqueued through hs_forward
+    itself -- no os.environ, no process-wide switch -- once per tile sort, once with the look-back depth passes in ticket
+    order and once with every field 0, each into workspaces of its own, ALL in flight before anybody waits: what VERDICT r6
+    asked for as "two rasterizers, different sorts, one process".  point_list, ranges and the image bit for bit the same,
+    hs_counters.reserved[5] = the tile sort asked for; and each equals what the Python host renders with the matching
+    environment variable set (which it turns into the same fields: _lib.sort_options)."""
+    import ctypes as C
+    from casualhdrsplat_amd import _lib as L
+    lib = L.load()
+    sc = S.make_scene(20000, 500, 300, 1, seed=3)
+    rast, leaf, call = _rasterizer_and_inputs(sc, None, requires_grad=True)
+    out = call()
+    st = out[0].grad_fn.st          # the finished forward's argument struct, dims and layout: the template
+    R, lay, d = st.num_rendered, st.layout, st.dims
+    assert R > 4 * 20000 and d.capacity == R
+    vt = ((d.W + 15) // 16) * ((d.H + 15) // 16)
+    stream = torch.cuda.current_stream().cuda_stream
+    forms = dict(radix=dict(tile_sort=L.HS_TILE_SORT_RADIX), count=dict(tile_sort=L.HS_TILE_SORT_COUNT),
+                 hier=dict(tile_sort=L.HS_TILE_SORT_HIER),
+                 passes_tickets=dict(tile_sort=L.HS_TILE_SORT_RADIX, depth_sort=L.HS_DEPTH_SORT_PASSES, chain_order=L.HS_CHAIN_TICKETS),
+                 auto={})
+    before = {k: os.environ.get(k) for k in ("HS_TILE_SORT", "HS_DEPTH_SORT", "HS_SCAN_IN_EMISSION")}
+    tickets_before, depth_before = lib.hs_sort_tickets(-1), lib.hs_depth_sort(-1)
+    bufs = {}
+    for name, sel in forms.items():
+        a = L.hs_fwd_args.from_buffer_copy(st.fwd_args)
+        geom, binning, image = torch.empty_like(st.geom), torch.empty_like(st.binning), torch.empty_like(st.image)
+        color, radii = torch.empty_like(out[0].detach()), torch.empty_like(out[1])
+        a.geom, a.binning, a.image, a.out_color, a.radii = (t.data_ptr() for t in (geom, binning, image, color, radii))
+        a.out_hdr = a.out_invdepth = a.counters_host = None
+        a.stages = L.HS_STAGE_ALL
+        a.tile_sort = a.depth_sort = a.chain_order = a.emission_scan = a.depth_range_cap = a.depth_dist_max = 0
+        for k, v in sel.items():
+            setattr(a, k, v)
+        L.check(lib.hs_forward(C.byref(a), stream), f"hs_forward[{name}]")
+        bufs[name] = (geom, binning, color, image, radii)
+    torch.cuda.synchronize()
+    assert before == {k: os.environ.get(k) for k in before}
+    assert (tickets_before, depth_before) == (lib.hs_sort_tickets(-1), lib.hs_depth_sort(-1))
+    got = {}
+    for name, (geom, binning, color, _, _) in bufs.items():
+        ctr = geom[lay.counters:lay.counters + 32].view(torch.int32).cpu().numpy()
+        assert int(ctr[0]) == R and int(ctr[1]) == 0, (name, ctr)
+        got[name] = dict(tile_sort=int(ctr[7]),
+                         point_list=binning[lay.point_list:lay.point_list + 4 * R].view(torch.int32).cpu().numpy(),
+                         ranges=binning[lay.ranges:lay.ranges + 8 * vt].view(torch.int32).reshape(vt, 2).cpu().numpy(),
+                         color=color.cpu().numpy())
+    assert {k: v["tile_sort"] for k, v in got.items()} == dict(radix=0, count=1, hier=2, passes_tickets=0, auto=1)
+    for name in forms:
+        for k in ("point_list", "ranges"):
+            assert np.array_equal(got[name][k], got["radix"][k]), (name, k)
+        assert np.array_equal(Hh.bits(got[name]["color"]), Hh.bits(got["radix"]["color"])), name
+    assert np.array_equal(Hh.bits(got["auto"]["color"]), Hh.bits(out[0].detach().cpu().numpy()))
+    # ... and through the Python host, which reads the environment's switches and fills the same fields
+    for name, env in dict(radix=dict(HS_TILE_SORT="radix"), count=dict(HS_TILE_SORT="count"), hier=dict(HS_TILE_SORT="hier"),
+                          passes_tickets=dict(HS_TILE_SORT="radix", HS_DEPTH_SORT="lsd")).items():
+        try:
+            if name == "passes_tickets":
+                lib.hs_sort_tickets(1)
+            with environment(**env):
+                g = Hh.run_hip(sc)
+        finally:
+            lib.hs_sort_tickets(tickets_before)
+        assert int(g["state"]["tile_sort"]) == got[name]["tile_sort"] and g["state"]["num_rendered"] == R, name
+        assert np.array_equal(g["state"]["point_list"][:R], got[name]["point_list"]), name
+        assert np.array_equal(g["state"]["ranges"], got[name]["ranges"]), name
+        assert np.array_equal(Hh.bits(g["color"]), Hh.bits(got[name]["color"])), name
 
 
 @pytest.mark.parametrize("form", ["hier", "radix"])
@@ -648,7 +718,7 @@ def test_skewed_scene_vs_oracle(oracle, form):
     contract, through the hierarchical tile sort and through the radix passes."""
     sc = skewed_scene()
     f, b = Hh.run_oracle(oracle, sc)
-    with tile_sort(form):
+    with environment(HS_TILE_SORT=form):
         g = Hh.run_hip(sc)
     st = g["state"]
     R = f["R"]
@@ -683,7 +753,7 @@ def test_hierarchical_tile_sort_equals_the_radix_passes_at_full_size(cfg):
     cams = S.blur_poses(W, H, 8) if cfg == "c4" else None
     out = {}
     for form in ("radix", "hier"):
-        with tile_sort(form):
+        with environment(HS_TILE_SORT=form):
             out[form] = Hh.run_hip(sc, cameras=cams, hdr=True)
         torch.cuda.empty_cache()
     a, b = out["radix"], out["hier"]
@@ -697,21 +767,6 @@ def test_hierarchical_tile_sort_equals_the_radix_passes_at_full_size(cfg):
     for k in a:
         if k != "state" and a[k] is not None:
             assert np.array_equal(Hh.bits(a[k]) if a[k].dtype == np.float32 else a[k], Hh.bits(b[k]) if b[k].dtype == np.float32 else b[k]), k
-
-
-@contextlib.contextmanager
-def environment(**kv):
-    """os.environ[k] = v for the forwards inside (the library reads these switches at every forward)."""
-    was = {k: os.environ.get(k) for k in kv}
-    os.environ.update({k: str(v) for k, v in kv.items()})
-    try:
-        yield
-    finally:
-        for k, v in was.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def _depth_sort_case(name):
@@ -827,7 +882,7 @@ def test_hierarchical_tile_sort_at_its_key_limits(W, H, n_poses, want):
     cams = S.blur_poses(W, H, n_poses, step=0.01) if n_poses > 1 else None
     out = {}
     for form in ("radix", "hier"):
-        with tile_sort(form):
+        with environment(HS_TILE_SORT=form):
             out[form] = Hh.run_hip(sc, cameras=cams)
     a, b = out["radix"], out["hier"]
     assert int(a["state"]["tile_sort"]) == 0 and int(b["state"]["tile_sort"]) == want
@@ -858,13 +913,8 @@ def test_counting_tile_sort_edges_vs_oracle(oracle, P, W, H, n_poses):
                              for k, f in enumerate(fs)])
     got = {}
     for mode in ("count", "radix"):
-        os.environ.pop("HS_TILE_SORT", None)
-        if mode == "radix":
-            os.environ["HS_TILE_SORT"] = "radix"
-        try:
+        with environment(HS_TILE_SORT="radix" if mode == "radix" else None):
             g = Hh.run_hip(sc, cameras=cams if n_poses > 1 else None, capacity=R + 5)
-        finally:
-            os.environ.pop("HS_TILE_SORT", None)
         st = g["state"]
         assert st["num_rendered"] == R
         assert np.array_equal(st["point_list"][:R].astype(np.int64), pl), mode
@@ -1726,21 +1776,14 @@ def test_randomized_configurations_vs_oracle(oracle):
         c = Hh.sweep_case(rng, case)
         # (these frames are small: by default their pairs are sorted by counting; one case in three keeps the radix passes,
         # one in three takes the hierarchical sort of large frames -- round 6 -- down to a handful of super-tiles)
-        os.environ.pop("HS_TILE_SORT", None)
-        if case % 3:
-            os.environ["HS_TILE_SORT"] = ("radix", "hier")[case % 3 - 1]
         # (and one case in four sorts its instances by depth with the look-back passes instead of by counting)
-        os.environ.pop("HS_DEPTH_SORT", None)
-        if case % 4 == 3:
-            os.environ["HS_DEPTH_SORT"] = "lsd"
         try:
-            _sweep_case_vs_oracle(oracle, c, case)
+            with environment(HS_TILE_SORT=(None, "radix", "hier")[case % 3], HS_DEPTH_SORT="lsd" if case % 4 == 3 else None):
+                _sweep_case_vs_oracle(oracle, c, case)
         except AssertionError as e:
             failures.append(f"{c['what']}: {e}")
             if os.environ.get("HS_PARITY_REPORT"):
                 print("SWEEP FAILED", failures[-1], flush=True)
-    os.environ.pop("HS_TILE_SORT", None)
-    os.environ.pop("HS_DEPTH_SORT", None)
     assert not failures, f"{len(failures)} failing case(s):\n" + "\n".join(failures)
 
 
@@ -1836,11 +1879,10 @@ def test_sweep_seed24_case9_giant_footprint(oracle):
         c = Hh.sweep_case(rng, case)
     assert c["what"].startswith("case 9: P=1085 28x161 deg=1 poses=1 hdr=True seed=999 act=exp dom=hdr"), c["what"]
     assert "wild=True" in c["what"]
-    os.environ.pop("HS_TILE_SORT", None)
-    os.environ.pop("HS_DEPTH_SORT", None)
     f = Hh.run_oracle(oracle, c["sc"], backward=False, radiance_activation="exp")[0]
     assert f["radii"].max() > 2500                      # the giant footprint is there
-    _sweep_case_vs_oracle(oracle, c, 9, sweep_bar=False)
+    with environment(HS_TILE_SORT=None, HS_DEPTH_SORT=None):
+        _sweep_case_vs_oracle(oracle, c, 9, sweep_bar=False)
 
 
 # (rows on the first pass's strict bar, measured on the MI355X: each scene's own share less half a per cent)
