@@ -98,9 +98,25 @@ class hs_loss_args(C.Structure):
                 ("dL_dloss", _fp), ("dL_dimage", _fp)]
 
 
+HS_ADAM_MAX_GROUPS = 16
+HS_ADAM_MASK_NONE, HS_ADAM_MASK_RADII, HS_ADAM_MASK_BYTES = 0, 1, 2
+
+
+class hs_adam_group(C.Structure):
+    _fields_ = [("param", _fp), ("grad", _fp), ("exp_avg", _fp), ("exp_avg_sq", _fp),
+                ("rows", C.c_int64), ("row_stride", C.c_int64), ("col_begin", C.c_int64), ("col_count", C.c_int64),
+                ("masked", C.c_int32), ("reserved", C.c_int32)]
+
+
+class hs_adam_args(C.Structure):
+    _fields_ = [("groups", C.POINTER(hs_adam_group)), ("n_groups", C.c_int32), ("mask_kind", C.c_int32),
+                ("mask", _fp), ("mask_len", C.c_int64), ("state", _fp), ("hyper", _fp)]
+
+
 EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
            "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
-           "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward")
+           "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
+           "hs_adam_state_bytes", "hs_adam_step")
 HS_RENDER_STATS = 24
 
 _lib = None
@@ -156,6 +172,10 @@ def load() -> C.CDLL:
     lib.hs_photometric_loss.restype = C.c_int
     lib.hs_photometric_loss_backward.argtypes = [C.POINTER(hs_loss_args), C.c_void_p]
     lib.hs_photometric_loss_backward.restype = C.c_int
+    lib.hs_adam_state_bytes.argtypes = [C.c_int32]
+    lib.hs_adam_state_bytes.restype = C.c_int64
+    lib.hs_adam_step.argtypes = [C.POINTER(hs_adam_args), C.c_void_p]
+    lib.hs_adam_step.restype = C.c_int
     if os.environ.get("HS_SORT_TICKETS", "")[:1] == "1":   # the process default of the chain order, set once
         lib.hs_sort_tickets(1)
     _lib = lib

@@ -10,6 +10,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
 
     python examples/train_synthetic.py --steps 300
     python examples/train_synthetic.py --steps 300 --lambda-dssim 0.2     # the published L1 + D-SSIM loss, fused
+    python examples/train_synthetic.py --steps 300 --fused-adam           # the update through optim.GaussianAdam, visible rows only
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -27,6 +28,7 @@ import torch
 
 from casualhdrsplat_amd import synthetic as S
 from casualhdrsplat_amd.losses import photometric_loss
+from casualhdrsplat_amd.optim import GaussianAdam
 from casualhdrsplat_amd.graphs import GraphedStep
 from casualhdrsplat_amd.image_formation import (FrameRasterizers, HDRBlurFormation, ImplicitCRF, TrajectorySpline,
                                                   knots_from_lookat)
@@ -52,10 +54,13 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
-        graph=False, capacity=None, lambda_dssim=0.0):
+        graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
-    losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1."""
+    losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
+    fused_adam: the update goes through optim.GaussianAdam -- one launch for all four tensors, and the per-Gaussian ones
+    (radiance, opacities) only in the rows some frame of the step saw (radii > 0 in any frame).  With graph=True the update
+    stays outside the captured step."""
     dev = torch.device(device)
     sc = S.make_scene(P, W, H, deg, seed=seed, hdr=True)
     cam = sc.camera
@@ -93,9 +98,15 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     fixed = {k: cloud_true[k] for k in ("means3D", "scales", "rotations")}
     with torch.no_grad():
         model.log_exposure[0] = truth.log_exposure[0]       # the gauge (see the module docstring)
-    opt = torch.optim.Adam([
-        {"params": [shs], "lr": 1e-2}, {"params": [raw_opac], "lr": 2e-2},
-        {"params": [model.log_exposure], "lr": 1e-2}, {"params": [model.trajectory.delta], "lr": 5e-4}])
+    if fused_adam:
+        opt = GaussianAdam([
+            {"params": [shs], "lr": 1e-2, "per_gaussian": True}, {"params": [raw_opac], "lr": 2e-2, "per_gaussian": True},
+            {"params": [model.log_exposure], "lr": 1e-2}, {"params": [model.trajectory.delta], "lr": 5e-4}])
+    else:
+        opt = torch.optim.Adam([
+            {"params": [shs], "lr": 1e-2}, {"params": [raw_opac], "lr": 2e-2},
+            {"params": [model.log_exposure], "lr": 1e-2}, {"params": [model.trajectory.delta], "lr": 5e-4}])
+    seen = torch.zeros(P, dtype=torch.bool, device=dev)      # Gaussians some frame of the step saw (written in place)
 
     def errors():
         with torch.no_grad():
@@ -115,7 +126,12 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         opac = torch.sigmoid(raw_opac)
         losses, mses = [], []
         for i in range(frames):
-            ldr, _, _, _ = model(i, fixed["means3D"], opac, shs, fixed["scales"], fixed["rotations"], cameras=cams)
+            ldr, _, radii, _ = model(i, fixed["means3D"], opac, shs, fixed["scales"], fixed["rotations"], cameras=cams)
+            if fused_adam:            # (kernels only, written in place: the captured step leaves no copy node behind)
+                if i == 0:
+                    torch.gt(radii, 0, out=seen)
+                else:
+                    seen.logical_or_(radii > 0)
             if lambda_dssim > 0:
                 losses.append(photometric_loss(ldr, targets[i], lambda_dssim))
             else:
@@ -147,7 +163,10 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             g0 = model.log_exposure.grad
             if g0 is not None:
                 g0[0] = 0.0                                    # frame 0's exposure is the gauge
-            opt.step()
+            if fused_adam:
+                opt.step(visibility=seen)
+            else:
+                opt.step()
         e_dt, e_pose = errors()
         hist.append(dict(step=it, loss=total / frames, psnr=ps / frames, exposure_log_err=e_dt, knot_pos_err=e_pose))
         if not quiet and (it % log_every == 0 or it == steps):
@@ -169,8 +188,12 @@ def main(argv=None):
     ap.add_argument("--graph", action="store_true", help="record the gradient computation once as a HIP graph and replay it")
     ap.add_argument("--lambda-dssim", type=float, default=0.0,
                     help="weight of the D-SSIM term of the published 3DGS loss (0.2 upstream; 0 = plain L1)")
+    ap.add_argument("--fused-adam", action="store_true",
+                    help="update through casualhdrsplat_amd.optim.GaussianAdam (one launch; per-Gaussian tensors only in the rows "
+                         "some frame of the step saw) instead of torch.optim.Adam")
     a = ap.parse_args(argv)
-    r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim)
+    r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
+            fused_adam=a.fused_adam)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

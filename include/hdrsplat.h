@@ -398,6 +398,69 @@ HS_API int hs_photometric_loss(const hs_loss_args* args, void* hip_stream);
 /* backward: dL_dimage = dL_dloss[0] * d loss / d image, from the partials of the forward of the same image / target */
 HS_API int hs_photometric_loss_backward(const hs_loss_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Adam update of the cloud and of any other fp32 parameters, fused into one launch
+ * and optionally restricted to the Gaussians a step saw (adam.hip).  Adam as torch.optim.Adam defines it: bias-corrected, no
+ * weight decay, no AMSGrad; fp32 parameters, gradients and moments.
+ *
+ * A GROUP is a column range [col_begin, col_begin + col_count) of a row-major fp32 matrix [rows, row_stride]: shs[P, M, 3]
+ * can be two groups with two learning rates (columns 0..2 and 3..3M-1) and stay one tensor.  Group g reads row g of the
+ * hyper-parameter table `hyper`, fp64 [n_groups][4] = {lr, beta1, beta2, eps}, ON THE DEVICE: a learning-rate schedule is a
+ * write to that table, also between replays of a captured graph.
+ *
+ * hs_adam_step enqueues two kernels and nothing else.  The first advances the device-resident state: with t the step
+ * count after the increment and B1 = beta1^t, B2 = beta2^t kept as RUNNING PRODUCTS in fp64 (B *= beta each step; 1 before
+ * the first),
+ *     step_size = (float)(lr / (1 - B1)),   bc2 = (float)sqrt(1 - B2)                      (fp64, then rounded)
+ * and b1 = (float)beta1, b2 = (float)beta2, c1 = (float)(1 - beta1), c2 = (float)(1 - beta2) (the difference in fp64, rounded
+ * once: an fp32 value, as torch passes it), e = (float)eps.  The second updates every element, in fp32, each operation a
+ * correctly rounded IEEE operation, nothing contracted, denormals kept, in exactly this order:
+ *     m' = b1 * m + c1 * g
+ *     v' = b2 * v + (c2 * g) * g
+ *     d  = sqrtf(v') / bc2 + e
+ *     p' = p - step_size * (m' / d)
+ * No atomics: the same inputs give the same bits.
+ *
+ * Visibility mask (optional): one entry per Gaussian, either the forward's radii (HS_ADAM_MASK_RADII: int32, visible = > 0)
+ * or bytes (HS_ADAM_MASK_BYTES: uint8 / bool, visible = != 0).  In a group flagged `masked`, rows whose entry is not visible
+ * are SKIPPED: param, exp_avg and exp_avg_sq keep their bits and are not read.  This is the published "sparse Adam" and is
+ * not dense Adam with a zero gradient: the moments of a skipped row do not decay and its momentum does not move it.  The
+ * step count is global to the call.  Groups not flagged `masked`, and every group when mask_kind is HS_ADAM_MASK_NONE, are
+ * dense.
+ *
+ * State: hs_adam_state_bytes(n_groups) = 64 + 64 * n_groups bytes, 16-byte aligned, owned by the caller.  All-zero bytes
+ * are a fresh state (t = 0).  Layout, for callers that save or restore it: u64 t at byte 0; for group g at byte 64 + 64 * g:
+ * fp64 B1, fp64 B2, then the eight fp32 values the first kernel derives (rewritten by every call).
+ * Pointers param / grad / exp_avg / exp_avg_sq need 4-byte alignment only (16-byte loads and stores are used where the
+ * addresses allow).  Limits (HS_EINVAL): 1 <= n_groups <= 16, rows >= 0 (0 = nothing to do, pointers not looked at),
+ * row_stride >= 1, col_begin >= 0, col_count >= 1, col_begin + col_count <= row_stride, rows * row_stride <= 2^40. */
+#define HS_ADAM_MAX_GROUPS 16
+#define HS_ADAM_MASK_NONE 0
+#define HS_ADAM_MASK_RADII 1
+#define HS_ADAM_MASK_BYTES 2
+typedef struct hs_adam_group {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t rows, row_stride, col_begin, col_count;
+    int32_t masked;               /* != 0: the mask applies to this group's rows (rows must equal mask_len) */
+    int32_t reserved;
+} hs_adam_group;
+
+typedef struct hs_adam_args {
+    const hs_adam_group* groups;  /* HOST array of n_groups descriptors (copied into the kernel's arguments) */
+    int32_t n_groups;
+    int32_t mask_kind;            /* HS_ADAM_MASK_* */
+    const void* mask;             /* device, mask_len entries; NULL with HS_ADAM_MASK_NONE */
+    int64_t mask_len;
+    void* state;                  /* device, hs_adam_state_bytes(n_groups) bytes */
+    const double* hyper;          /* device, [n_groups][4] = {lr, beta1, beta2, eps} */
+} hs_adam_args;
+
+/* -1 (HS_EINVAL) unless 1 <= n_groups <= HS_ADAM_MAX_GROUPS */
+HS_API int64_t hs_adam_state_bytes(int32_t n_groups);
+HS_API int hs_adam_step(const hs_adam_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
