@@ -113,10 +113,31 @@ class hs_adam_args(C.Structure):
                 ("mask", _fp), ("mask_len", C.c_int64), ("state", _fp), ("hyper", _fp)]
 
 
+HS_DENSIFY_MAX_MATRICES = 16
+HS_DENSIFY_RAW_OPACITY, HS_DENSIFY_RAW_SCALES = 1, 2
+HS_DENSIFY_COPY, HS_DENSIFY_ZERO_NEW, HS_DENSIFY_MEANS, HS_DENSIFY_SCALES = 0, 1, 2, 3
+HS_DENSIFY_KIND_SURVIVOR, HS_DENSIFY_KIND_CLONE, HS_DENSIFY_KIND_CHILD0, HS_DENSIFY_KIND_CHILD1 = 0, 1, 2, 3
+HS_DENSIFY_COUNTS = 8
+
+
+class hs_densify_matrix(C.Structure):
+    _fields_ = [("src", _fp), ("dst", _fp), ("row_stride", C.c_int64), ("role", C.c_int32), ("reserved", C.c_int32)]
+
+
+class hs_densify_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("P_out", C.c_int64), ("flags", C.c_int32), ("r_max", C.c_int32),
+                ("tau_grad", C.c_float), ("tau_split", C.c_float), ("o_min", C.c_float), ("sigma_max", C.c_float),
+                ("grad_accum", _fp), ("denom", _fp), ("max_radii", _fp), ("opacities", _fp), ("scales", _fp),
+                ("rotations", _fp), ("noise", _fp), ("workspace", _fp), ("row_map", _fp), ("counts", _fp),
+                ("counts_host", _fp), ("matrices", C.POINTER(hs_densify_matrix)), ("n_matrices", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
            "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
            "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
-           "hs_adam_state_bytes", "hs_adam_step")
+           "hs_adam_state_bytes", "hs_adam_step",
+           "hs_densify_workspace_bytes", "hs_densify_plan", "hs_densify_apply")
 HS_RENDER_STATS = 24
 
 _lib = None
@@ -176,6 +197,12 @@ def load() -> C.CDLL:
     lib.hs_adam_state_bytes.restype = C.c_int64
     lib.hs_adam_step.argtypes = [C.POINTER(hs_adam_args), C.c_void_p]
     lib.hs_adam_step.restype = C.c_int
+    lib.hs_densify_workspace_bytes.argtypes = [C.c_int64]
+    lib.hs_densify_workspace_bytes.restype = C.c_int64
+    lib.hs_densify_plan.argtypes = [C.POINTER(hs_densify_args), C.c_void_p]
+    lib.hs_densify_plan.restype = C.c_int
+    lib.hs_densify_apply.argtypes = [C.POINTER(hs_densify_args), C.c_void_p]
+    lib.hs_densify_apply.restype = C.c_int
     if os.environ.get("HS_SORT_TICKETS", "")[:1] == "1":   # the process default of the chain order, set once
         lib.hs_sort_tickets(1)
     _lib = lib

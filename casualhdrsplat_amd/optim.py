@@ -252,6 +252,32 @@ class GaussianAdam(torch.optim.Optimizer):
             self._build()
         self._sync_hyper()
 
+    def replace_params(self, mapping: dict) -> None:
+        """Swap tensors: `mapping` is {old parameter: (new parameter, exp_avg, exp_avg_sq)} -- what a densification hands
+        over (densify.densify_and_prune), the number of rows may differ.  The new tensors take the old ones' places in the
+        param groups, the per-parameter state and the launch order; the DEVICE step count and the running products beta^t
+        are not touched, so the next step is the one an uninterrupted run would take (rebuilding the optimizer through
+        load_state_dict would re-seed the products with pow)."""
+        for old, (new, m, v) in mapping.items():
+            if not any(q is old for g in self.param_groups for q in g["params"]):
+                raise ValueError("GaussianAdam.replace_params: a tensor to replace is not one of the optimizer's parameters")
+            for t, what in ((new, "parameter"), (m, "exp_avg"), (v, "exp_avg_sq")):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_contiguous():
+                    raise ValueError(f"GaussianAdam.replace_params: the new {what} must be a contiguous float32 tensor")
+                _require_gpu(t, f"the new {what}")
+            if m.shape != new.shape or v.shape != new.shape or new.shape[1:] != old.shape[1:]:
+                raise ValueError("GaussianAdam.replace_params: exp_avg / exp_avg_sq must have the new parameter's shape, and the "
+                                 "new parameter the old one's shape behind dim 0")
+            if not new.is_leaf:
+                raise ValueError("can't optimize a non-leaf Tensor")
+        for old, (new, m, v) in mapping.items():
+            for g in self.param_groups:
+                g["params"] = [new if q is old else q for q in g["params"]]
+            st = self.state.pop(old, {})
+            self.state[new] = {"step": st.get("step", torch.tensor(0.0, dtype=torch.float32)), "exp_avg": m, "exp_avg_sq": v}
+            if self._entries is not None:
+                self._entries = [(gi, new if q is old else q) for gi, q in self._entries]
+
     # ---- the step ----
 
     def enqueue(self, visibility: torch.Tensor | None = None) -> None:

@@ -132,6 +132,14 @@ class DensifyStats:
     def reset(self) -> None:
         self.grad_accum.zero_(); self.denom.zero_(); self.max_radii.zero_()
 
+    def resize(self, P: int) -> None:
+        """Zeroed statistics for a cloud of P Gaussians on the same device (after densify_and_prune changed P: the rows
+        moved, and upstream starts every densification interval from zero)."""
+        dev = self.grad_accum.device
+        self.grad_accum = torch.zeros(P, dtype=torch.float32, device=dev)
+        self.denom = torch.zeros(P, dtype=torch.float32, device=dev)
+        self.max_radii = torch.zeros(P, dtype=torch.int32, device=dev)
+
 
 _HELPED_FRAMES = [0]      # frames of this process whose binning stage reported look-back helps (hs_counters.reserved[4])
 _PINNED_POOL: list = []  # recycled page-locked int32[8] buffers (one hs_counters each) (hipHostMalloc per step is slow)

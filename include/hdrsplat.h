@@ -461,6 +461,107 @@ typedef struct hs_adam_args {
 HS_API int64_t hs_adam_state_bytes(int32_t n_groups);
 HS_API int hs_adam_step(const hs_adam_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Densify / prune of the cloud (densify.hip): the published densify_and_prune --
+ * clone, split into N = 2 children, prune -- as a PLAN stage (which rows come out, and from which source row) and an APPLY
+ * stage (one gather of every row of every array).  Between the two the caller reads P_out and allocates: the contract is the
+ * file's -- the caller owns every byte, nothing here synchronises or allocates.  No atomics anywhere: the same inputs give
+ * the same bits.
+ *
+ * Per source row i of P (fp32 throughout, every operation one correctly rounded IEEE operation, nothing contracted):
+ *     g   = grad_accum[i] / denom[i];  g counts as 0 when denom[i] == 0 or the quotient is NaN
+ *     sel = g >= tau_grad
+ *     s   = max of the three stored scales: s = scales[3i]; if (scales[3i+1] > s) s = scales[3i+1]; the same for [3i+2]
+ *     big = s > tau_split
+ *     prune(o, r, s) = o < o_min || (r_max > 0 && r > r_max) || (sigma on && s > sigma_max)
+ *   not sel      the row survives iff !prune(o_i, r_i, s)
+ *   sel && !big  CLONE: the row survives and a bit-identical copy is appended, both iff !prune(o_i, r_i, s)
+ *   sel && big   SPLIT: the source row goes; children k = 0, 1 exist, both, iff !prune(o_i, r_i, child(s)), where child(x) is
+ *                x / 1.6f, or with HS_DENSIFY_RAW_SCALES x - HS_DENSIFY_LOG_1_6 (the fp32 constant logf(1.6))
+ * with o_i = opacities[i], r_i = max_radii[i]: derived rows are tested with their SOURCE's radius.  Opacities and scales
+ * are compared AS STORED: with HS_DENSIFY_RAW_OPACITY the stored value is a logit and o_min is one too, with
+ * HS_DENSIFY_RAW_SCALES the stored values are logs and tau_split / sigma_max are logs too (sigmoid and exp are monotonic: the
+ * host converts the thresholds once, in fp64, and rounds to fp32; no transcendental function decides anything).  The sigma
+ * test is off when sigma_max is +INFINITY, and with stored-linear scales also when it is 0; the radius test when r_max is 0.
+ *
+ * Output order: survivors | clones | children k = 0 | children k = 1, each in source order.  Output row j carries
+ *     row_map[j] = kind << 30 | source row      (HS_DENSIFY_KIND_*: 0 survivor, 1 clone, 2 child k = 0, 3 child k = 1)
+ * and counts[HS_DENSIFY_COUNTS] (u32) = {P_out, survivors, clones, children (both k), sources that left no row at all, split
+ * sources (sel && big, whether or not their children exist), P, 0}.
+ *
+ * hs_densify_plan enqueues three kernels: classify (a 2-bit code per row into the workspace, four counts per block of 256
+ * rows), one small scan of the block counts (writes `counts`), and the map (writes row_map[0, P_out); its first thread also
+ * leaves a copy of `counts` at counts_host, a page-locked host address as hs_fwd_args.counters_host is, when given).
+ * Workspace: hs_densify_workspace_bytes(P) = align256(P) + 16 * ceil(P / 256) bytes, 16-byte aligned; row_map holds 2 * P
+ * u32 (P_out <= 2 P).
+ *
+ * hs_densify_apply enqueues ONE kernel over up to 16 matrices {src [P, row_stride], dst [P_out, row_stride], role}; output
+ * row j of every matrix is written from source row row_map[j] & (2^30 - 1), and nothing is written at or beyond row P_out:
+ *   HS_DENSIFY_COPY      every row copied
+ *   HS_DENSIFY_ZERO_NEW  survivors copied, every new row (clone, child) all zeros: Adam's moments
+ *   HS_DENSIFY_SCALES    row_stride 3: children get child(x) of each stored scale, other rows are copied
+ *   HS_DENSIFY_MEANS     row_stride 3: other rows copied; child k of source i gets, with (w, x, y, z) = rotations[4i..]
+ *                        divided by n = sqrtf(((w w + x x) + y y) + z z), sg_j = scales[3i + j] (expf of it with
+ *                        HS_DENSIFY_RAW_SCALES), v_j = sg_j * noise[6i + 3k + j], and the rotation matrix
+ *                          R00 = 1 - 2 (y y + z z)   R01 = 2 (x y - w z)       R02 = 2 (x z + w y)
+ *                          R10 = 2 (x y + w z)       R11 = 1 - 2 (x x + z z)   R12 = 2 (y z - w x)
+ *                          R20 = 2 (x z - w y)       R21 = 2 (y z + w x)       R22 = 1 - 2 (x x + y y)
+ *                        mean_c = ((Rc0 v_0 + Rc1 v_1) + Rc2 v_2) + src[3i + c], in exactly this order
+ * `noise` is [P, 2, 3] standard normals indexed by the SOURCE row: the library holds no random-number generator.  The scales
+ * and rotations the means read are the SOURCE arrays of the args (not a matrix's dst).  16-byte loads and stores are used
+ * where the addresses allow, 4-byte accesses of exactly the owned elements otherwise: src / dst need 4-byte alignment only.
+ * Limits (HS_EINVAL, reported before any HIP call): 0 <= P < 2^30, 0 <= P_out <= 2 P, 1 <= n_matrices <= 16, row_stride >= 1
+ * (3 for MEANS / SCALES), P_out * row_stride < 2^40; with P == 0 (or, in apply, P_out == 0) no data pointer is looked at. */
+#define HS_DENSIFY_MAX_MATRICES 16
+#define HS_DENSIFY_RAW_OPACITY 1
+#define HS_DENSIFY_RAW_SCALES 2
+#define HS_DENSIFY_COPY 0
+#define HS_DENSIFY_ZERO_NEW 1
+#define HS_DENSIFY_MEANS 2
+#define HS_DENSIFY_SCALES 3
+#define HS_DENSIFY_KIND_SURVIVOR 0
+#define HS_DENSIFY_KIND_CLONE 1
+#define HS_DENSIFY_KIND_CHILD0 2
+#define HS_DENSIFY_KIND_CHILD1 3
+#define HS_DENSIFY_COUNTS 8
+#define HS_DENSIFY_LOG_1_6 0.47000366f /* logf(1.6f) rounded to fp32: bits 0x3ef0a452 */
+typedef struct hs_densify_matrix {
+    const float* src;             /* [P, row_stride] */
+    float* dst;                   /* [P_out, row_stride]; must not overlap src */
+    int64_t row_stride;           /* floats per row */
+    int32_t role;                 /* HS_DENSIFY_COPY / _ZERO_NEW / _MEANS / _SCALES */
+    int32_t reserved;
+} hs_densify_matrix;
+
+typedef struct hs_densify_args {
+    int64_t P;                    /* source rows */
+    int64_t P_out;                /* apply: rows of every dst = counts[0] of the plan (the plan ignores it) */
+    int32_t flags;                /* HS_DENSIFY_RAW_* */
+    int32_t r_max;                /* prune rows whose max_radii exceeds it; 0 = off */
+    float tau_grad;               /* select rows whose mean gradient reaches it */
+    float tau_split;              /* stored space: split above, clone at or below */
+    float o_min;                  /* stored space: prune below */
+    float sigma_max;              /* stored space: prune above; +INFINITY (or 0 with linear scales) = off */
+    const float* grad_accum;      /* [P]  plan */
+    const float* denom;           /* [P]  plan */
+    const int32_t* max_radii;     /* [P]  plan */
+    const float* opacities;       /* [P]  plan */
+    const float* scales;          /* [P, 3]  plan, and the apply's MEANS role */
+    const float* rotations;       /* [P, 4] (w, x, y, z), not normalised: apply, MEANS role */
+    const float* noise;           /* [P, 2, 3]: apply, MEANS role */
+    void* workspace;              /* hs_densify_workspace_bytes(P) bytes, 16-byte aligned: plan */
+    uint32_t* row_map;            /* [2 P]: written by the plan, read by the apply */
+    uint32_t* counts;             /* device, [HS_DENSIFY_COUNTS]: written by the plan */
+    uint32_t* counts_host;        /* NULL, or a page-locked host address the GPU can write: the plan's copy of counts */
+    const hs_densify_matrix* matrices; /* HOST array of n_matrices descriptors (copied into the kernel's arguments): apply */
+    int32_t n_matrices;
+    int32_t reserved;
+} hs_densify_args;
+
+/* align256(P) + 16 * ceil(P / 256); -1 (HS_EINVAL) unless 0 <= P < 2^30 */
+HS_API int64_t hs_densify_workspace_bytes(int64_t P);
+HS_API int hs_densify_plan(const hs_densify_args* args, void* hip_stream);
+HS_API int hs_densify_apply(const hs_densify_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
