@@ -133,11 +133,19 @@ class hs_densify_args(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class hs_activate_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("g_begin", C.c_int64), ("g_end", C.c_int64),
+                ("opacity_raw", _fp), ("scales_raw", _fp), ("rotations_raw", _fp),
+                ("opacities", _fp), ("scales", _fp), ("rotations", _fp),
+                ("dL_dopacities", _fp), ("dL_dscales", _fp), ("dL_drotations", _fp)]
+
+
 EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
            "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
            "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
            "hs_adam_state_bytes", "hs_adam_step",
-           "hs_densify_workspace_bytes", "hs_densify_plan", "hs_densify_apply")
+           "hs_densify_workspace_bytes", "hs_densify_plan", "hs_densify_apply",
+           "hs_activate", "hs_activate_backward")
 HS_RENDER_STATS = 24
 
 _lib = None
@@ -203,6 +211,10 @@ def load() -> C.CDLL:
     lib.hs_densify_plan.restype = C.c_int
     lib.hs_densify_apply.argtypes = [C.POINTER(hs_densify_args), C.c_void_p]
     lib.hs_densify_apply.restype = C.c_int
+    lib.hs_activate.argtypes = [C.POINTER(hs_activate_args), C.c_void_p]
+    lib.hs_activate.restype = C.c_int
+    lib.hs_activate_backward.argtypes = [C.POINTER(hs_activate_args), C.c_void_p]
+    lib.hs_activate_backward.restype = C.c_int
     if os.environ.get("HS_SORT_TICKETS", "")[:1] == "1":   # the process default of the chain order, set once
         lib.hs_sort_tickets(1)
     _lib = lib

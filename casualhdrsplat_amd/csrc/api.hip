@@ -230,6 +230,24 @@ static int check_loss_shape(int32_t planes, int32_t H, int32_t W, float lambda, 
     return HS_OK;
 }
 
+// hs_activate_args: the limits on P, and one tensor's pointers -- present (its `key` pointer given) means every pointer in
+// `need` is given, and every given pointer is 4-byte aligned
+static int check_activate_rows(const hs_activate_args* a, const char* who) {
+    if (!a) { set_error("%s: null args", who); return HS_EINVAL; }
+    if (a->P < 0 || a->P >= (1ll << 30)) { set_error("%s: P=%lld outside [0, 2^30)", who, (long long)a->P); return HS_EINVAL; }
+    return HS_OK;
+}
+
+static int check_activate_tensor(const char* who, const char* name, const void* key, const void* const* need, const char* const* need_names, int n) {
+    if (!key) return HS_OK;
+    if ((uintptr_t)key & 3) { set_error("%s: %s must be 4-byte aligned", who, name); return HS_EINVAL; }
+    for (int i = 0; i < n; ++i) {
+        if (!need[i]) { set_error("%s: %s is given but %s is NULL", who, name, need_names[i]); return HS_EINVAL; }
+        if ((uintptr_t)need[i] & 3) { set_error("%s: %s must be 4-byte aligned", who, need_names[i]); return HS_EINVAL; }
+    }
+    return HS_OK;
+}
+
 }  // namespace hs
 
 using namespace hs;
@@ -478,6 +496,39 @@ int hs_photometric_loss_backward(const hs_loss_args* a, void* hip_stream) {
         return HS_EINVAL;
     }
     return launch_loss_bwd(*a, (hipStream_t)hip_stream);
+}
+
+int hs_activate(const hs_activate_args* a, void* hip_stream) {
+    const char* who = "hs_activate";
+    int rc = check_activate_rows(a, who);
+    if (rc) return rc;
+    if (a->P == 0) return HS_OK;       // (no pointer is looked at)
+    const void* o[] = {a->opacities}; const char* on[] = {"opacities"};
+    const void* s[] = {a->scales}; const char* sn[] = {"scales"};
+    const void* r[] = {a->rotations}; const char* rn[] = {"rotations"};
+    if ((rc = check_activate_tensor(who, "opacity_raw", a->opacity_raw, o, on, 1))) return rc;
+    if ((rc = check_activate_tensor(who, "scales_raw", a->scales_raw, s, sn, 1))) return rc;
+    if ((rc = check_activate_tensor(who, "rotations_raw", a->rotations_raw, r, rn, 1))) return rc;
+    return launch_activate_fwd(*a, (hipStream_t)hip_stream);
+}
+
+int hs_activate_backward(const hs_activate_args* a, void* hip_stream) {
+    const char* who = "hs_activate_backward";
+    int rc = check_activate_rows(a, who);
+    if (rc) return rc;
+    if (a->g_begin < 0 || a->g_begin > a->g_end || a->g_end > a->P) {
+        set_error("%s: rows [g_begin=%lld, g_end=%lld) are not inside [0, P=%lld]", who, (long long)a->g_begin, (long long)a->g_end,
+                  (long long)a->P);
+        return HS_EINVAL;
+    }
+    if (a->g_begin == a->g_end) return HS_OK;
+    const void* o[] = {a->opacities}; const char* on[] = {"opacities"};
+    const void* s[] = {a->scales}; const char* sn[] = {"scales"};
+    const void* r[] = {a->rotations, a->rotations_raw}; const char* rn[] = {"rotations", "rotations_raw"};
+    if ((rc = check_activate_tensor(who, "dL_dopacities", a->dL_dopacities, o, on, 1))) return rc;
+    if ((rc = check_activate_tensor(who, "dL_dscales", a->dL_dscales, s, sn, 1))) return rc;
+    if ((rc = check_activate_tensor(who, "dL_drotations", a->dL_drotations, r, rn, 2))) return rc;
+    return launch_activate_bwd(*a, (hipStream_t)hip_stream);
 }
 
 int64_t hs_sort_tmp_bytes(int64_t n) { return sort_tmp_bytes(n) + 256 + 2 * align_up(n * 8, 256) + 2 * align_up(n * 4, 256); }

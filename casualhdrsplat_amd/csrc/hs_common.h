@@ -108,6 +108,9 @@ int launch_sh_backward_views(int P, int M, int deg, int V, const float* means3D,
 int64_t loss_pair_count(int planes, int H, int W);
 int launch_loss_fwd(const hs_loss_args& a, hipStream_t s);
 int launch_loss_bwd(const hs_loss_args& a, hipStream_t s);
+// activations of the stored cloud (activate.hip); the arguments are checked by the entry points (api.hip)
+int launch_activate_fwd(const hs_activate_args& a, hipStream_t s);
+int launch_activate_bwd(const hs_activate_args& a, hipStream_t s);
 
 // Scratch of the single-sweep radix passes (binning.hip): digit totals in kGhistCopies copies of [pass <= 8][256], one
 // ticket counter per pass (a block's place in the look-back chain), then one status word per (pass, block, digit).

@@ -237,11 +237,36 @@ class _Pending:
         return n
 
 
+_NEEDS_GPU = "casualhdrsplat_amd rasterizes on an MI355X only: tensors must live on a cuda (HIP) device"
+PARAMETERIZATIONS = ("activated", "raw")
+
+
+def _activate(P: int, op_raw, sc_raw, ro_raw, dev):
+    """parameterization="raw": the activated tensors of the stored ones (hs_activate, one kernel) -- sigmoid of the logit
+    opacities, exp of the log scales, the quaternions normalised as torch.nn.functional.normalize does -- in scratch tensors
+    of the stored tensors' shapes.  `sc_raw` / `ro_raw` are None with a precomputed covariance."""
+    if dev.type != "cuda":
+        raise RuntimeError(_NEEDS_GPU)
+    for name, t, cols in (("opacities", op_raw, 1), ("scales", sc_raw, 3), ("rotations", ro_raw, 4)):
+        if t is not None and t.numel() != P * cols:
+            raise ValueError(f"parameterization='raw': {name} has {t.numel()} elements, expected {P} x {cols}")
+    a = L.hs_activate_args()
+    a.P = P
+    op = _empty(tuple(op_raw.shape), torch.float32, dev, "opacities")
+    sc = None if sc_raw is None else _empty(tuple(sc_raw.shape), torch.float32, dev, "scales")
+    ro = None if ro_raw is None else _empty(tuple(ro_raw.shape), torch.float32, dev, "rotations")
+    a.opacity_raw, a.scales_raw, a.rotations_raw = _ptr(op_raw), _ptr(sc_raw), _ptr(ro_raw)
+    a.opacities, a.scales, a.rotations = _ptr(op), _ptr(sc), _ptr(ro)
+    if P > 0:
+        L.check(L.load().hs_activate(C.byref(a), _stream()), "hs_activate")
+    return op, sc, ro
+
+
 def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, shs, colors_precomp, scales,
                  rotations, cov3D_precomp, exposure, crf_table, capacity: Optional[int], want_invdepth: bool = False):
     dev = means3D.device
     if dev.type != "cuda":
-        raise RuntimeError("casualhdrsplat_amd rasterizes on an MI355X only: tensors must live on a cuda (HIP) device")
+        raise RuntimeError(_NEEDS_GPU)
     P = means3D.shape[0]
     W, H = int(settings.image_width), int(settings.image_height)
     if settings.viewmatrices is not None:
@@ -420,7 +445,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         sc = _f32c(scales, dev) if scales is not None and scales.numel() else None
         ro = _f32c(rotations, dev) if rotations is not None and rotations.numel() else None
         cv = _f32c(cov3Ds_precomp, dev) if cov3Ds_precomp is not None and cov3Ds_precomp.numel() else None
+        # parameterization="raw": opacities / scales / rotations arrive as the trainer stores them; the pipeline runs on
+        # their activated values and the backward converts its gradients to the stored ones inside the flat buffer
+        raw = None
         with _on_device(dev):  # kernels are launched on the tensors' GPU, whatever the current device is
+            if aux is not None and aux.get("raw"):
+                raw = (op, sc, ro)
+                op, sc, ro = _activate(m3.shape[0], op, sc, ro, dev)
             color, hdr, radii, st, exp_t, crf_t, invd = _run_forward(raster_settings, m3, op, shs, cp, sc, ro, cv,
                                                                      exposure, crf_table, capacity, return_invdepth)
         ctx.st = st
@@ -460,7 +491,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.pose_shapes = (tuple(viewmats.shape), tuple(projmats.shape), tuple(camposes.shape))
         ctx.has = (shs is not None, cp is not None, sc is not None, cv is not None, exposure is not None,
                    crf_table is not None)
-        ctx.save_for_backward(m3, op, shs, cp, sc, ro, cv, exp_t, crf_t)
+        ctx.raw = raw is not None
+        ctx.save_for_backward(m3, op, shs, cp, sc, ro, cv, exp_t, crf_t, *(raw or ()))
         ctx.mark_non_differentiable(radii)
         ctx.n_out = (hdr is not None, bool(return_alpha), bool(return_invdepth))
         outs = (color, radii) + ((hdr,) if hdr is not None else ())
@@ -492,8 +524,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ginvd = _f32c(grad_invd, dev) if grad_invd is not None else None
         want_pose = any(ctx.needs_input_grad[10:13])
         with _on_device(dev):
-            g = _launch_backward(st, saved, gcol, ghdr, L.HS_BWD_ALL, want_pose, galpha,
-                                 defer_sh=ctx.deferred is not None, ginvd=ginvd, densify=ctx.densify,
+            g = _launch_backward(st, saved[:9], gcol, ghdr, L.HS_BWD_ALL, want_pose, galpha,
+                                 raw=saved[9:12] if ctx.raw else None, defer_sh=ctx.deferred is not None, ginvd=ginvd, densify=ctx.densify,
                                  gather_group=None if ctx.deferred is None else ctx.deferred.get("gather_group"),
                                  gather_direct=bool(ctx.deferred.get("gather_direct")) if ctx.deferred else False,
                                  reduce_group=None if ctx.aux is None else ctx.aux.get("reduce_group"),
@@ -552,12 +584,19 @@ class _RasterizeGaussians(torch.autograd.Function):
 
 def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bool = False, galpha=None,
                      defer_sh: bool = False, ginvd=None, densify=None, gather_group=None, stats=None,
-                     timeline=None, gather_direct: bool = False, reduce_group=None, reduce_chunks: int = 0) -> dict:
+                     timeline=None, gather_direct: bool = False, reduce_group=None, reduce_chunks: int = 0,
+                     raw=None) -> dict:
     """Enqueue hs_backward.  All per-Gaussian gradients are carved out of ONE flat fp32 buffer (the
     layout casualhdrsplat_amd.distributed all-reduces in a single RCCL call): [means3D | opacities | colors | scales |
     rotations | cov3D | exposure | crf_table | sh | means2D | pose gradients].  means2D -- the screen-space
     gradient of THIS view, a densification statistic and not a parameter gradient -- comes after everything a
-    view-parallel step sums over the ranks, so the summed set is one contiguous span without it."""
+    view-parallel step sums over the ranks, so the summed set is one contiguous span without it.
+
+    `raw` (parameterization="raw": the stored opacities, scales, rotations of the forward): the opacities / scales / rotations
+    slices are converted in place to gradients with respect to the stored tensors (hs_activate_backward), directly behind
+    the kernels that write them -- per chunk of Gaussians where the backward runs in chunks, BEFORE the chunk's collective
+    starts: the conversion is linear and every rank holds the same parameters, so the sum of converted rows is the
+    converted sum."""
     lib = L.load()
     m3, op, shs, cp, sc, ro, cv, exp_t, crf_t = saved
     dev = m3.device
@@ -614,6 +653,18 @@ def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bo
                                                               _ptr(g["camposes"]))
     a.dL_dview_colors = _ptr(g["view_colors"])
     a.dL_dout_invdepth = _ptr(ginvd)
+    to_stored = None
+    if raw is not None:
+        b = L.hs_activate_args()
+        b.P = P
+        b.rotations_raw = _ptr(raw[2])
+        b.opacities, b.scales, b.rotations = _ptr(op), _ptr(sc), _ptr(ro)
+        b.dL_dopacities, b.dL_dscales, b.dL_drotations = _ptr(g["opacities"]), _ptr(g["scales"]), _ptr(g["rotations"])
+
+        def to_stored(g0, g1):
+            b.g_begin, b.g_end = int(g0), int(g1)
+            L.check(lib.hs_activate_backward(C.byref(b), _stream()), "hs_activate_backward")
+
     if densify is not None:
         if densify.grad_accum.shape[0] != P or densify.grad_accum.device != dev:
             raise ValueError("DensifyStats was created for a different number of Gaussians or another device")
@@ -632,6 +683,8 @@ def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bo
         g["_gather"] = D.start_view_gather(g["view_colors"], st.camposes, gather_group, direct=gather_direct)
         a.stages = L.HS_BWD_PROJECT
         L.check(lib.hs_backward(C.byref(a), _stream()), "hs_backward[project]")
+        if to_stored is not None:
+            to_stored(0, P)
         a.stages = stages
     elif reduce_group is not None and reduce_chunks > 0 and stages == L.HS_BWD_ALL:
         # view-parallel step with the plain (all-reduce) exchange: the per-Gaussian half runs in ascending chunks of the
@@ -645,6 +698,8 @@ def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bo
         def project(g0, g1):
             a.g_begin, a.g_end = int(g0), int(g1)
             L.check(lib.hs_backward(C.byref(a), _stream()), "hs_backward[project chunk]")
+            if to_stored is not None:
+                to_stored(g0, g1)
 
         rows = [g[k] for k in ("means3D", "opacities", "colors_precomp", "scales", "rotations", "cov3D_precomp", "shs")
                 if g[k] is not None]
@@ -654,6 +709,8 @@ def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bo
         a.g_begin, a.g_end, a.stages = 0, 0, stages
     else:
         L.check(lib.hs_backward(C.byref(a), _stream()), "hs_backward")
+        if to_stored is not None and stages == L.HS_BWD_ALL:
+            to_stored(0, P)
     return g
 
 
@@ -675,10 +732,11 @@ def replay_forward(out_tensor: torch.Tensor, stages: int = L.HS_STAGE_RENDER) ->
 def replay_backward(out_tensor: torch.Tensor, grad_color: torch.Tensor, stages: int = L.HS_BWD_ALL,
                     grad_hdr: Optional[torch.Tensor] = None) -> dict:
     """Profiling helper (bench.py's per-kernel roofline leg): re-enqueue the selected half of the
-    backward of the forward call that produced `out_tensor`, outside autograd."""
+    backward of the forward call that produced `out_tensor`, outside autograd.  Of a parameterization="raw" call too the
+    gradients returned are those with respect to the ACTIVATED opacities, scales and rotations: what the kernels write."""
     fn = out_tensor.grad_fn
     dev = out_tensor.device
-    return _launch_backward(fn.st, fn.saved_tensors, _f32c(grad_color, dev),
+    return _launch_backward(fn.st, fn.saved_tensors[:9], _f32c(grad_color, dev),
                             None if grad_hdr is None else _f32c(grad_hdr, dev), stages)
 
 
@@ -692,7 +750,8 @@ def render_stats(out_tensor: torch.Tensor, grad_color: torch.Tensor, grad_hdr: O
     """Profiling helper (bench.py's lane-utilisation / VALU-roofline leg): replays the render forward and backward of
     the call that produced `out_tensor` with the counting instantiation of the kernels (hs_render_stats) and returns
     the counters by name: (wave, entry) trips of the two compositing loops, how many found no active lane, the sum
-    of active pixels (<= 128 per trip), entries removed by the half-tile test, staged entries and batches."""
+    of active pixels (<= 128 per trip), entries removed by the half-tile test, staged entries and batches.  (Of a
+    parameterization="raw" call it replays the render kernels on the activated tensors of that call: nothing is converted.)"""
     fn = out_tensor.grad_fn
     st: _State = fn.st
     dev = out_tensor.device
@@ -707,7 +766,7 @@ def render_stats(out_tensor: torch.Tensor, grad_color: torch.Tensor, grad_hdr: O
     d = st.dims
     n_wg = ((d.W + L.HS_TILE - 1) // L.HS_TILE) * ((d.H + L.HS_TILE - 1) // L.HS_TILE) * d.n_poses
     tl = torch.zeros(n_wg, 3, dtype=torch.int64, device=dev) if timeline else None
-    _launch_backward(st, fn.saved_tensors, _f32c(grad_color, dev), None if grad_hdr is None else _f32c(grad_hdr, dev),
+    _launch_backward(st, fn.saved_tensors[:9], _f32c(grad_color, dev), None if grad_hdr is None else _f32c(grad_hdr, dev),
                      L.HS_BWD_RENDER, stats=stats, timeline=tl)
     vals = stats.cpu().tolist()
     res = dict(zip(RENDER_STAT_NAMES, vals))
@@ -771,15 +830,25 @@ class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings, capacity: Optional[int] = None,
                  return_alpha: bool = False, defer_sh_grad: bool = False, return_invdepth: bool = False,
                  densify_stats: Optional[DensifyStats] = None, gather_group=None, keep_state: bool = False,
-                 reduce_group=None, reduce_chunks: int = 4):
+                 reduce_group=None, reduce_chunks: int = 4, parameterization: str = "activated"):
         super().__init__()
+        # extension: "raw" = forward() takes opacities, scales and rotations AS A TRAINER STORES THEM -- logits, logs,
+        # unnormalised quaternions: the tensors optim.GaussianAdam updates and densify_and_prune compacts -- activates them
+        # inside the library (hs_activate: sigmoid, exp, torch.nn.functional.normalize) and returns gradients with respect
+        # to the stored tensors, inside the flat gradient buffer.  The stored tensors are then leaves: their .grads are
+        # views of that buffer, and a chunked all-reduce may stay in flight behind backward() (reduce_group below).
+        # With cov3D_precomp only the opacities are stored; shs, colors_precomp and means3D are what they always were.
+        if parameterization not in PARAMETERIZATIONS:
+            raise ValueError(f"parameterization must be one of {PARAMETERIZATIONS}, got {parameterization!r}")
+        self.parameterization = parameterization
         # view-parallel training with the plain exchange (every rank renders its own view; the per-Gaussian gradients
         # are summed over the ranks): a torch.distributed process group (or True for the default group) makes the
         # backward run its per-Gaussian half in `reduce_chunks` ascending chunks and start the all-reduce of each
         # chunk's gradient rows while the next chunk computes; call finish_reduce() before reading any gradient.
         # The collectives outlive backward() only when every differentiable input is a leaf without a .grad (autograd
-        # then just stores what it is given); with activations between the parameters and the rasterizer, or gradient
-        # accumulation, backward() itself waits for them before autograd touches the rows (finish_reduce() returns 0)
+        # then just stores what it is given); with torch activations between the parameters and the rasterizer (pass the
+        # stored tensors to a parameterization="raw" rasterizer instead), or gradient accumulation, backward() itself
+        # waits for them before autograd touches the rows (finish_reduce() returns 0)
         self.reduce_group = reduce_group
         self.reduce_chunks = int(reduce_chunks)
         # with defer_sh_grad: a torch.distributed process group (or True for the default group) makes the backward
@@ -864,6 +933,8 @@ class GaussianRasterizer(nn.Module):
                 self.deferred["gather_group"] = self.gather_group
                 self.deferred["gather_direct"] = bool(self.gather_direct)
             aux = {"keep_state": self.keep_state, "cell": self._cell}
+            if self.parameterization == "raw":
+                aux["raw"] = True
             if self.reduce_group is not None and not self.defer_sh_grad:
                 aux["reduce_group"], aux["reduce_chunks"] = self.reduce_group, self.reduce_chunks
             outs = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
@@ -933,7 +1004,11 @@ def inspect_state(out_tensor) -> dict:
     n_img = d.n_poses + (1 if d.n_poses > 1 else 0)
     pose_hdr = (view(st.image, lay.pose_hdr, n_img * 3 * d.W * d.H, torch.float32).reshape(n_img, 3, d.H, d.W)
                 if ((st.flags & L.HS_FLAG_HDR) or d.n_poses > 1) else None)
+    # (st.keep as _run_forward fills it)
+    _, _, _, kept_opacities, _, _, kept_scales, kept_rotations, _ = st.keep
     return dict(
+        # the opacities / scales / rotations the pipeline ran on (parameterization="raw": what hs_activate wrote)
+        opacities=kept_opacities, scales=kept_scales, rotations=kept_rotations,
         pose_hdr=pose_hdr,
         num_rendered=R,
         look_back_helps=int(view(st.geom, lay.counters, 8, torch.int32)[6].item()),   # hs_counters.reserved[4]

@@ -45,6 +45,16 @@ class GaussianCloud:
                  rotations=self.rotations / self.rotations.norm(dim=1, keepdim=True).clamp_min(1e-12))
         return {k: (v.to(device) if device is not None else v).contiguous() for k, v in d.items()}
 
+    def stored(self, device=None) -> Dict[str, torch.Tensor]:
+        """The five tensors in the STORED parameterisation -- logit opacities, log scales, unnormalised quaternions -- under
+        the argument names of optim.cloud_param_groups: what a trainer updates (optim.GaussianAdam), compacts
+        (densify_and_prune, whose thresholds are compared in this space) and hands to
+        GaussianRasterizer(..., parameterization="raw") as they are.  Detached copies on `device`; the caller sets
+        requires_grad."""
+        d = dict(means3D=self.means3D, opacities=self.opacity_logit, shs=self.shs, scales=self.log_scales,
+                 rotations=self.rotations)
+        return {k: v.detach().to(device=device, dtype=torch.float32).contiguous().clone() for k, v in d.items()}
+
 
 def _property_names(M: int):
     names = ["x", "y", "z", "nx", "ny", "nz"] + [f"f_dc_{i}" for i in range(3)]

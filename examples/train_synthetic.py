@@ -11,11 +11,13 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300
     python examples/train_synthetic.py --steps 300 --lambda-dssim 0.2     # the published L1 + D-SSIM loss, fused
     python examples/train_synthetic.py --steps 300 --fused-adam           # the update through optim.GaussianAdam, visible rows only
+    python examples/train_synthetic.py --steps 300 --fused-adam --raw     # the stored (logit) opacities go straight into the rasterizer
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
 """
 import argparse
+import functools
 import math
 import os
 import sys
@@ -30,6 +32,7 @@ from casualhdrsplat_amd import synthetic as S
 from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.optim import GaussianAdam
 from casualhdrsplat_amd.graphs import GraphedStep
+from casualhdrsplat_amd.rasterizer import GaussianRasterizer
 from casualhdrsplat_amd.image_formation import (FrameRasterizers, HDRBlurFormation, ImplicitCRF, TrajectorySpline,
                                                   knots_from_lookat)
 
@@ -54,13 +57,16 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
-        graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False):
+        graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
     fused_adam: the update goes through optim.GaussianAdam -- one launch for all four tensors, and the per-Gaussian ones
     (radiance, opacities) only in the rows some frame of the step saw (radii > 0 in any frame).  With graph=True the update
-    stays outside the captured step."""
+    stays outside the captured step.
+    raw: the learner's rasterizers take the cloud as it is STORED (GaussianRasterizer(..., parameterization="raw")): the
+    logit opacities go in as the leaf they are -- no torch.sigmoid in front, their gradient a view of the rasterizer's flat
+    buffer -- and the fixed scales / rotations as logs / quaternions."""
     dev = torch.device(device)
     sc = S.make_scene(P, W, H, deg, seed=seed, hdr=True)
     cam = sc.camera
@@ -84,8 +90,10 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     # the learner: the response curve is given, everything else starts off
     # --graph: one persistent sync-free rasterizer per captured frame, so that the step's gradient computation can be
     # recorded once and replayed (graphs.GraphedStep): no host time for the few thousand tiny kernels of the pose arithmetic
-    per_frame = FrameRasterizers(capacity=capacity or 40 * P * virtual) if graph else None
-    model = formation(ImplicitCRF(K=128), **({"rasterizer_factory": per_frame} if graph else {}))
+    how = {"parameterization": "raw"} if raw else {}
+    per_frame = FrameRasterizers(capacity=capacity or 40 * P * virtual, **how) if graph else None
+    factory = per_frame if graph else (functools.partial(GaussianRasterizer, **how) if raw else None)
+    model = formation(ImplicitCRF(K=128), **({"rasterizer_factory": factory} if factory is not None else {}))
     model.crf.load_state_dict(truth.crf.state_dict())
     for p_ in model.crf.parameters():
         p_.requires_grad_(False)
@@ -96,6 +104,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     shs = shs0.to(dev).requires_grad_(True)
     raw_opac = raw_opac0.to(dev).requires_grad_(True)
     fixed = {k: cloud_true[k] for k in ("means3D", "scales", "rotations")}
+    if raw:                                                  # (the stored form of the fixed tensors: the quaternions as they are)
+        fixed["scales"] = fixed["scales"].log()
     with torch.no_grad():
         model.log_exposure[0] = truth.log_exposure[0]       # the gauge (see the module docstring)
     if fused_adam:
@@ -123,7 +133,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         # one pass over the spline for all frames (its few hundred tiny tensor operations are the step's host cost), one
         # rasterizer call per frame, one backward of the summed loss
         cams = model.cameras_all()
-        opac = torch.sigmoid(raw_opac)
+        opac = raw_opac if raw else torch.sigmoid(raw_opac)
         losses, mses = [], []
         for i in range(frames):
             ldr, _, radii, _ = model(i, fixed["means3D"], opac, shs, fixed["scales"], fixed["rotations"], cameras=cams)
@@ -191,9 +201,12 @@ def main(argv=None):
     ap.add_argument("--fused-adam", action="store_true",
                     help="update through casualhdrsplat_amd.optim.GaussianAdam (one launch; per-Gaussian tensors only in the rows "
                          "some frame of the step saw) instead of torch.optim.Adam")
+    ap.add_argument("--raw", action="store_true",
+                    help="pass the stored (logit) opacities to GaussianRasterizer(..., parameterization='raw') instead of "
+                         "torch.sigmoid in front of the default rasterizer")
     a = ap.parse_args(argv)
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
-            fused_adam=a.fused_adam)
+            fused_adam=a.fused_adam, raw=a.raw)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

@@ -562,6 +562,46 @@ HS_API int64_t hs_densify_workspace_bytes(int64_t P);
 HS_API int hs_densify_plan(const hs_densify_args* args, void* hip_stream);
 HS_API int hs_densify_apply(const hs_densify_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Activations of the STORED cloud (activate.hip).  A trainer stores logit opacities,
+ * log scales and unnormalised quaternions -- what hs_adam_step updates and hs_densify_* compact -- while hs_forward /
+ * hs_backward take opacities, scales and unit quaternions.  hs_activate computes the second from the first; hs_activate_backward
+ * turns the gradients hs_backward wrote into gradients with respect to the stored values, IN PLACE.  One kernel each; the
+ * caller owns every byte, nothing is allocated, nothing synchronises.  fp32, every operation one correctly rounded IEEE
+ * operation plus the library expf, nothing contracted, denormals kept, no atomics: the same inputs give the same bits.
+ *
+ * hs_activate, rows [0, P) of every tensor whose STORED pointer is not NULL (its activated pointer must then be given):
+ *     opacities[i]   = 1 / (1 + expf(-opacity_raw[i]))
+ *     scales[j]      = expf(scales_raw[j])                                     j in [0, 3 P)
+ *     n              = max(sqrtf(((q0 q0 + q1 q1) + q2 q2) + q3 q3), 1e-12f)   q = rotations_raw[4 i ..]
+ *     rotations[4 i + k] = q_k / n                                             (torch.nn.functional.normalize's clamp)
+ * hs_activate_backward, rows [g_begin, g_end) of every tensor whose GRADIENT pointer is not NULL (its activated pointer, and
+ * for the rotations the stored one, must then be given), with o / s / q^ the activated values hs_activate wrote:
+ *     dL_dopacities[i] <- (g o) (1 - o)
+ *     dL_dscales[j]    <- g s
+ *     d = ((q^0 g0 + q^1 g1) + q^2 g2) + q^3 g3;   dL_drotations[4 i + k] <- (g_k - q^_k d) / n
+ *     with n recomputed from the stored q as above; where the clamp was active (|q| < 1e-12f) g_k <- g_k / 1e-12f
+ * Each element is read and written by the same thread.  The map is linear in g: converting the rows of a chunk before they are
+ * summed over ranks that hold the same parameters gives the sum's conversion.
+ * Every pointer needs 4-byte alignment only (16-byte accesses are used where the addresses allow, 4-byte accesses of exactly
+ * the rows' elements otherwise).  Limits (HS_EINVAL, reported before any HIP call): 0 <= P < 2^30, 0 <= g_begin <= g_end <= P.
+ * P == 0, an empty range and a call with no tensor present are successful no-ops. */
+typedef struct hs_activate_args {
+    int64_t P;                    /* rows of every tensor */
+    int64_t g_begin, g_end;       /* hs_activate_backward: the rows to convert (hs_activate ignores them) */
+    const float* opacity_raw;     /* [P]     logits          NULL = absent */
+    const float* scales_raw;      /* [P, 3]  logs            NULL = absent */
+    const float* rotations_raw;   /* [P, 4]  (w, x, y, z), any length */
+    float* opacities;             /* [P]     written by hs_activate, read by hs_activate_backward */
+    float* scales;                /* [P, 3] */
+    float* rotations;             /* [P, 4] */
+    float* dL_dopacities;         /* [P]     hs_activate_backward, in place   NULL = absent */
+    float* dL_dscales;            /* [P, 3] */
+    float* dL_drotations;         /* [P, 4] */
+} hs_activate_args;
+
+HS_API int hs_activate(const hs_activate_args* args, void* hip_stream);
+HS_API int hs_activate_backward(const hs_activate_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
