@@ -33,7 +33,7 @@ _fp = C.c_void_p  # device pointers travel as plain addresses
 
 class hs_dims(C.Structure):
     _fields_ = [("P", C.c_int32), ("M", C.c_int32), ("sh_degree", C.c_int32), ("W", C.c_int32), ("H", C.c_int32),
-                ("n_poses", C.c_int32), ("capacity", C.c_int64), ("crf_K", C.c_int32), ("reserved", C.c_int32)]
+                ("n_poses", C.c_int32), ("capacity", C.c_int64), ("crf_K", C.c_int32), ("n_frames", C.c_int32)]
 
 
 class hs_sizes(C.Structure):
@@ -145,7 +145,11 @@ EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward"
            "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
            "hs_adam_state_bytes", "hs_adam_step",
            "hs_densify_workspace_bytes", "hs_densify_plan", "hs_densify_apply",
-           "hs_activate", "hs_activate_backward")
+           "hs_activate", "hs_activate_backward", "hs_max_frames")
+# detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a
+# library without it reads hs_dims.n_frames as the reserved word it was and would render all poses into ONE image, silently
+# -- max_frames() is what a request for frames is checked against
+OPTIONAL_EXPORTS = ("hs_max_frames",)
 HS_RENDER_STATS = 24
 
 _lib = None
@@ -163,7 +167,7 @@ def load() -> C.CDLL:
             "casualhdrsplat_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
     for name in EXPORTS:
-        if not hasattr(lib, name):
+        if not hasattr(lib, name) and name not in OPTIONAL_EXPORTS:
             raise RuntimeError(f"{LIB_PATH} does not export {name}")
     lib.hs_version.restype = C.c_int
     if lib.hs_version() != HS_VERSION:   # (a stale variant picked by HS_LIB_PATH would read the structs short or long)
@@ -215,6 +219,9 @@ def load() -> C.CDLL:
     lib.hs_activate.restype = C.c_int
     lib.hs_activate_backward.argtypes = [C.POINTER(hs_activate_args), C.c_void_p]
     lib.hs_activate_backward.restype = C.c_int
+    if hasattr(lib, "hs_max_frames"):
+        lib.hs_max_frames.argtypes = []
+        lib.hs_max_frames.restype = C.c_int
     if os.environ.get("HS_SORT_TICKETS", "")[:1] == "1":   # the process default of the chain order, set once
         lib.hs_sort_tickets(1)
     _lib = lib
@@ -262,8 +269,24 @@ def check(rc: int, what: str) -> None:
         raise RuntimeError(f"{what} failed (code {rc}): {msg}")
 
 
-def plan(P: int, M: int, sh_degree: int, W: int, H: int, n_poses: int, capacity: int, crf_K: int = 0):
-    d = hs_dims(P, M, sh_degree, W, H, n_poses, capacity, crf_K, 0)
+def max_frames() -> int:
+    """The largest hs_dims.n_frames the loaded library groups poses into; 0: it has no hs_max_frames and ignores the field."""
+    lib = load()
+    return int(lib.hs_max_frames()) if hasattr(lib, "hs_max_frames") else 0
+
+
+def require_frames(n_frames: int) -> None:
+    """RuntimeError unless the loaded library renders `n_frames` frames in one call."""
+    if n_frames > 1 and n_frames > max_frames():
+        raise RuntimeError(f"{LIB_PATH} " + ("does not export hs_max_frames: it ignores hs_dims.n_frames and would render the "
+                           f"poses of all {n_frames} frames into one image" if max_frames() == 0 else
+                           f"groups at most {max_frames()} frames, {n_frames} were asked for") +
+                           "; rebuild it (`make -C casualhdrsplat_amd/csrc`) or render the frames one call each")
+
+
+def plan(P: int, M: int, sh_degree: int, W: int, H: int, n_poses: int, capacity: int, crf_K: int = 0, n_frames: int = 0):
+    require_frames(n_frames)
+    d = hs_dims(P, M, sh_degree, W, H, n_poses, capacity, crf_K, n_frames)
     sz, lay = hs_sizes(), hs_layout()
     check(load().hs_plan(C.byref(d), C.byref(sz), C.byref(lay)), "hs_plan")
     return d, sz, lay

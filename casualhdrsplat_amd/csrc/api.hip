@@ -107,10 +107,16 @@ int64_t pose_partial_floats(int P, int N);
 
 static int plan(const hs_dims& d, hs_sizes* sz, hs_layout* L) {
     if (d.P < 0 || d.W <= 0 || d.H <= 0 || d.n_poses < 1 || d.capacity < 0 || d.M < 0 || d.crf_K < 0 || d.crf_K > 4096 ||
-        d.crf_K == 1 || d.n_poses > 21845) {
+        d.crf_K == 1 || d.n_poses > kMaxPoses) {
         set_error("hs_plan: bad dims P=%d W=%d H=%d N=%d capacity=%lld", d.P, d.W, d.H, d.n_poses, (long long)d.capacity);
         return HS_EINVAL;
     }
+    // frames: F consecutive runs of n_poses / F poses (0 = 1: the call without frames)
+    if (d.n_frames < 0 || d.n_frames > d.n_poses || (d.n_frames > 1 && d.n_poses % d.n_frames != 0)) {
+        set_error("hs_plan: n_frames=%d must lie in [0, n_poses=%d] and divide n_poses", d.n_frames, d.n_poses);
+        return HS_EINVAL;
+    }
+    const int F = frames_of(d), npf = d.n_poses / F;
     const int64_t I = (int64_t)d.P * d.n_poses;
     const int64_t gx = (d.W + kTile - 1) / kTile, gy = (d.H + kTile - 1) / kTile;
     const int64_t vtiles = gx * gy * d.n_poses;
@@ -158,7 +164,8 @@ static int plan(const hs_dims& d, hs_sizes* sz, hs_layout* L) {
     o = 0;
     l.final_T = carve(HW * d.n_poses * 4);
     l.n_contrib = carve(HW * d.n_poses * 4);
-    l.pose_hdr = carve(HW * 3 * 4 * (d.n_poses + (d.n_poses > 1 ? 1 : 0)));
+    // one radiance plane per pose, then (frames of more than one pose) one mean-radiance plane per frame
+    l.pose_hdr = carve(HW * 3 * 4 * (d.n_poses + (npf > 1 ? F : 0)));
     l.tile_work = carve(vtiles * 4);
     l.tile_order = carve(vtiles * 4);
     sz->image_bytes = o;
@@ -263,6 +270,8 @@ int hs_plan(const hs_dims* dims, hs_sizes* sizes, hs_layout* layout) {
     return plan(*dims, sizes, layout);
 }
 
+int hs_max_frames(void) { return kMaxPoses; }   // (the limit on n_poses: every pose may be a frame of its own)
+
 int hs_forward(const hs_fwd_args* a, void* hip_stream) {
     if (!a) { set_error("hs_forward: null args"); return HS_EINVAL; }
     hipStream_t s = (hipStream_t)hip_stream;
@@ -347,6 +356,11 @@ int hs_backward(const hs_bwd_args* a, void* hip_stream) {
     int rc = plan(a->dims, &sz, &L);
     if (rc) return rc;
     if ((rc = check_flags(a->flags, "hs_backward"))) return rc;
+    if (frames_of(a->dims) > 1 && (a->dL_dout_alpha || a->dL_dout_invdepth)) {
+        set_error("hs_backward: dL_dout_alpha / dL_dout_invdepth are per-image gradients and are not supported with n_frames=%d",
+                  a->dims.n_frames);
+        return HS_EINVAL;
+    }
     rc = check_common(a->dims, a->means3D, a->shs, a->colors_precomp, a->scales, a->rotations, a->cov3D_precomp,
                       a->viewmatrices, a->projmatrices, a->camposes, a->bg, "hs_backward");
     if (rc) return rc;

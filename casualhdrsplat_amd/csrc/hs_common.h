@@ -65,6 +65,10 @@ constexpr int kSortTileMin = kPairTile;                     // smallest radix ti
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 static inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
+// most poses of a call (hdrsplat.h: n_poses <= 21845), hence most frames: every pose may be a frame of its own (hs_max_frames)
+constexpr int kMaxPoses = 21845;
+// frames of a call (hs_dims.n_frames, 0 = 1): F consecutive runs of n_poses / F poses, each with its own exposure and image
+static inline int frames_of(const hs_dims& d) { return d.n_frames > 1 ? d.n_frames : 1; }
 
 // index of highest set bit + 1 (number of bits needed for values < n ... as upstream getHigherMsb)
 static inline int tile_bits(uint32_t n) {
@@ -290,31 +294,37 @@ __device__ __forceinline__ float wave_sum_hi_f32(float v) {
 
 // Second stage of the CRF-table / exposure gradient (render.hip, crf_grad_kernel): the partial rows of the pixel blocks
 // added in a fixed order, one wave per output element (3K table entries + the exposure): lanes stride over the rows of the
-// blocks that worked on that channel -- every pose, every pixel block --, then a fixed DPP tree: reproducible.  Run either
+// blocks that worked on that channel -- every frame, every pose, every pixel block --, then a fixed DPP tree: reproducible.  Run either
 // by crf_reduce_kernel or, when the same hs_backward call goes on to the segmented sum, by the first workgroups of
 // pair_segsum_kernel (one launch less on the backward's critical path).
 struct CrfReduce {
     const float* partials; int bx, planes, K; float* d_table; float* d_exposure;
-    int nblocks;   // 256-thread workgroups the job takes: ceil((3K + 1) / 4); 0 = nothing to do
+    int nblocks;   // 256-thread workgroups the job takes: ceil((3K + F) / 4); 0 = nothing to do
+    int F;         // frames of the call (hs_dims.n_frames): the planes are frame-major, planes / F of them per frame
 };
 __device__ __forceinline__ void crf_reduce_block(const CrfReduce& c, int block) {
     const int K = c.K;
-    const int i = block * 4 + (threadIdx.x >> 6);  // 0 .. 3K: table entry ch * K + k, or 3K = exposure
+    const int i = block * 4 + (threadIdx.x >> 6);  // 0 .. 3K - 1: table entry ch * K + k; 3K + f: exposure of frame f
     const int lane = threadIdx.x & 63;
-    if (i > 3 * K) return;
-    const bool expo = i == 3 * K;
+    if (i >= 3 * K + c.F) return;
+    const bool expo = i >= 3 * K;
     const int ch = expo ? 0 : i / K, k = expo ? K : i - ch * K;
     float acc = 0.f;
-    // rows of plane p = [p * bx, (p + 1) * bx); plane p carries channel p % 3
-    const int nrows = expo ? c.planes * c.bx : (c.planes / 3) * c.bx;
+    // rows of plane p = [p * bx, (p + 1) * bx); plane p carries channel p % 3; the planes of frame f are the run
+    // [f * planes / F, (f + 1) * planes / F).  A table entry adds the rows of its channel over ALL planes (frame-major,
+    // inside a frame the order a call on that frame alone has), an exposure the rows of its own frame's planes only -- in
+    // the order, and so with the bits, of a call on that frame alone
+    const int frame_rows = (c.planes / c.F) * c.bx;
+    const int nrows = expo ? frame_rows : (c.planes / 3) * c.bx;
+    const int row0 = expo ? (i - 3 * K) * frame_rows : 0;
     for (int r = lane; r < nrows; r += 64) {
-        const int row = expo ? r : ((r / c.bx) * 3 + ch) * c.bx + (r % c.bx);
+        const int row = expo ? row0 + r : ((r / c.bx) * 3 + ch) * c.bx + (r % c.bx);
         acc += c.partials[(int64_t)row * (K + 1) + k];
     }
     acc = wave_sum_hi_f32(acc);
     if (lane == 63) {
         if (!expo) { if (c.d_table) c.d_table[i] = acc; }
-        else if (c.d_exposure) c.d_exposure[0] = acc;
+        else if (c.d_exposure) c.d_exposure[i - 3 * K] = acc;
     }
 }
 

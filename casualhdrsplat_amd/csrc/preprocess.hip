@@ -449,6 +449,7 @@ struct PreBwd {
     float* d_means3D; float* d_means2D; float* d_opac; float* d_shs; float* d_colors; float* d_scales;
     float* d_rots; float* d_cov;
     float* dens_grad; float* dens_denom; int* dens_radii;  // densification statistics, updated in place, or null
+    int NF;                // poses per frame (N / hs_dims.n_frames; N without frames): the statistics count FRAMES
     float* pose_partials;  // [blocks][N][kPoseVals] or null
     int blk0;              // first block of this launch (hs_bwd_args.g_begin / kPreBwdBlock: a chunk of the Gaussians)
 };
@@ -602,6 +603,13 @@ __global__ void __launch_bounds__(kPreBwdBlock) HS_PB_OCC preprocess_bwd_kernel(
     }
 
     int max_radius = 0;  // over poses
+    // Frames (NF < N): the statistics are what one call per frame leaves -- at the last pose of every frame, |sum over the
+    // frame's poses of dL/dmean2D.xy| goes to grad_accum and 1 to denom if the frame rasterized the Gaussian at all.  A
+    // thread owns its Gaussian's entries, so the adds land in frame order like those of separate calls.
+    const bool dens_frames = p.dens_grad != nullptr && p.NF < p.N;
+    float fm2d[2] = {0.f, 0.f};
+    bool frame_on = false;
+    int frame_last = p.NF - 1;
     for (int pose = 0; pose < p.N; ++pose) {
         const int64_t idx = (int64_t)pose * p.P + g;
         const int rad = pose == 0 ? rad0 : (valid ? p.radii_inst[idx] : 0);
@@ -629,6 +637,7 @@ __global__ void __launch_bounds__(kPreBwdBlock) HS_PB_OCC preprocess_bwd_kernel(
             r9 = q2.y;
         }
         gm2d[0] += r[0]; gm2d[1] += r[1];
+        if (dens_frames) { fm2d[0] += r[0]; fm2d[1] += r[1]; frame_on = true; }
         if (!p.antialias) gop += r[5];
 
         const float* V = p.view + 16 * pose;
@@ -766,6 +775,13 @@ __global__ void __launch_bounds__(kPreBwdBlock) HS_PB_OCC preprocess_bwd_kernel(
             gcol_pre[0] += r[6]; gcol_pre[1] += r[7]; gcol_pre[2] += r[8];
         }
     }  // if (on)
+        if (dens_frames && pose == frame_last) {
+            if (frame_on) {   // (implies valid)
+                p.dens_grad[g] += sqrtf(fm2d[0] * fm2d[0] + fm2d[1] * fm2d[1]);
+                p.dens_denom[g] += 1.f;
+            }
+            fm2d[0] = 0.f; fm2d[1] = 0.f; frame_on = false; frame_last += p.NF;
+        }
         if constexpr (POSE) {
             // workgroup sum of the 27 pose terms (all threads take part: `on` is per thread, `want_pose` uniform)
             __syncthreads();  // s_sh rows are still being read above; the scratch below aliases nothing but keep order simple
@@ -827,8 +843,10 @@ __global__ void __launch_bounds__(kPreBwdBlock) HS_PB_OCC preprocess_bwd_kernel(
         for (int k = 0; k < 6; ++k) p.d_cov[6 * (int64_t)g + k] = gcov[k];
     }
     if (valid && p.dens_grad && max_radius > 0) {
-        p.dens_grad[g] += sqrtf(gm2d[0] * gm2d[0] + gm2d[1] * gm2d[1]);
-        p.dens_denom[g] += 1.f;
+        if (!dens_frames) {
+            p.dens_grad[g] += sqrtf(gm2d[0] * gm2d[0] + gm2d[1] * gm2d[1]);
+            p.dens_denom[g] += 1.f;
+        }
         p.dens_radii[g] = max(p.dens_radii[g], max_radius);
     }
     if (valid) {
@@ -1055,6 +1073,7 @@ int launch_preprocess_bwd(const hs_bwd_args& a, const hs_layout& L, hipStream_t 
     p.d_colors = a.dL_dcolors_precomp; p.d_scales = a.dL_dscales; p.d_rots = a.dL_drotations;
     p.d_cov = a.dL_dcov3D_precomp;
     p.dens_grad = a.densify_grad_accum; p.dens_denom = a.densify_denom; p.dens_radii = a.densify_max_radii;
+    p.NF = d.n_poses / frames_of(d);
     const bool shg = p.d_shs != nullptr;
     // hs_bwd_args.g_begin / g_end: this launch covers the Gaussians [g_lo, g_hi) (all of them by default); a step that
     // exchanges gradients chunk by chunk enqueues the chunks in ascending order

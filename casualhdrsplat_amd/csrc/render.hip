@@ -287,7 +287,7 @@ __device__ __forceinline__ void lane_pixels(int lane, int sx, int sy, int& px, i
 }
 
 struct RenderFwd {
-    int W, H, gx, ntiles, N, flags;
+    int W, H, gx, ntiles, N, flags;   // N: poses per FRAME (the launch covers frames x N poses)
     const uint2* ranges; const uint32_t* point_list; const float4* rec; const float* bg;
     float* out_color; float* out_hdr; float* final_T; uint32_t* n_contrib; float* pose_hdr;
     float* out_invdepth;  // [N,H,W] or null
@@ -385,16 +385,17 @@ __device__ __forceinline__ void write_pixel_fwd(const RenderFwd& p, const PixF& 
         float* ph = p.pose_hdr + (int64_t)pose * 3 * HW;
         ph[pix] = H0; ph[HW + pix] = H1; ph[2 * HW + pix] = H2;
     }
-    if (p.N == 1) {
+    if (p.N == 1) {   // one pose per frame: the pose IS the frame, its image and its exposure
+        float* const oc = p.out_color + (int64_t)pose * 3 * HW;
         if (hdr) {
             Crf c = p.crf;
-            c.dt = p.exposure[0];
-            if (p.out_hdr) { p.out_hdr[pix] = H0; p.out_hdr[HW + pix] = H1; p.out_hdr[2 * HW + pix] = H2; }
-            p.out_color[pix] = crf_eval(c, 0, H0);
-            p.out_color[HW + pix] = crf_eval(c, 1, H1);
-            p.out_color[2 * HW + pix] = crf_eval(c, 2, H2);
+            c.dt = p.exposure[pose];
+            if (p.out_hdr) { float* const oh = p.out_hdr + (int64_t)pose * 3 * HW; oh[pix] = H0; oh[HW + pix] = H1; oh[2 * HW + pix] = H2; }
+            oc[pix] = crf_eval(c, 0, H0);
+            oc[HW + pix] = crf_eval(c, 1, H1);
+            oc[2 * HW + pix] = crf_eval(c, 2, H2);
         } else {
-            p.out_color[pix] = H0; p.out_color[HW + pix] = H1; p.out_color[2 * HW + pix] = H2;
+            oc[pix] = H0; oc[HW + pix] = H1; oc[2 * HW + pix] = H2;
         }
     }
 }
@@ -635,24 +636,29 @@ render_fwd_kernel(RenderFwd p) {
     if constexpr (STATS) ws.flush(p.stats);
 }
 
-// N > 1: average the per-pose images.  LDR domain (default, follows assets/pipeline.png: the blur "+" is
-// drawn over the LDR images) or radiance domain (HS_FLAG_BLUR_HDR).  pose_hdr slot N receives mean radiance.
-__global__ void __launch_bounds__(256) resolve_kernel(int64_t HW, int N, int flags, float* pose_hdr, Crf crf,
+// N > 1: average the per-pose images of every frame (N = poses per frame, F frames: poses f N .. f N + N - 1 are frame
+// f's, in ascending order -- the arithmetic of a call on that frame alone).  LDR domain (default, follows
+// assets/pipeline.png: the blur "+" is drawn over the LDR images) or radiance domain (HS_FLAG_BLUR_HDR).  pose_hdr slot
+// F N + f receives frame f's mean radiance.
+__global__ void __launch_bounds__(256) resolve_kernel(int64_t HW, int N, int F, int flags, float* pose_hdr, Crf crf,
                                                       const float* exposure, float* out_color, float* out_hdr) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // over 3*HW
-    if (i >= 3 * HW) return;
-    const int ch = (int)(i / HW);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;  // over F*3*HW: element i of the [F,3,H,W] outputs
+    if (i >= (int64_t)F * 3 * HW) return;
+    const int f = (int)(i / (3 * HW));
+    const int64_t j = i - (int64_t)f * 3 * HW;                  // element of the frame's [3,H,W] image
+    const int ch = (int)(j / HW);
     const bool hdr = flags & HS_FLAG_HDR;
-    if (hdr) crf.dt = exposure[0];
+    if (hdr) crf.dt = exposure[f];
     float sumH = 0.f, sumL = 0.f;
+    const float* planes = pose_hdr + (int64_t)f * N * 3 * HW + j;
     for (int k = 0; k < N; ++k) {
-        const float Hv = pose_hdr[(int64_t)k * 3 * HW + i];
+        const float Hv = planes[(int64_t)k * 3 * HW];
         sumH += Hv;
         if (hdr && !(flags & HS_FLAG_BLUR_HDR)) sumL += crf_eval(crf, ch, Hv);
     }
     const float inv = 1.f / (float)N;
     const float meanH = sumH * inv;
-    pose_hdr[(int64_t)N * 3 * HW + i] = meanH;
+    pose_hdr[((int64_t)F * N + f) * 3 * HW + j] = meanH;
     if (hdr) {
         if (out_hdr) out_hdr[i] = meanH;
         out_color[i] = (flags & HS_FLAG_BLUR_HDR) ? crf_eval(crf, ch, meanH) : sumL * inv;
@@ -747,7 +753,8 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(int nb, int gx, int n
 constexpr int kCrfPixPerWave = 1024;
 
 struct CrfGradArgs {
-    int64_t HW; int N, flags; const float* pose_hdr; Crf crf; const float* exposure; const float* dL_dcolor; float* partials;
+    int64_t HW; int N, F, flags;   // N: poses per frame, F: frames
+    const float* pose_hdr; Crf crf; const float* exposure; const float* dL_dcolor; float* partials;
     int bx, planes;   // the job's workgroups: bx pixel blocks x planes (pose, channel) image planes
 };
 
@@ -763,14 +770,15 @@ __device__ __forceinline__ void crf_grad_body(const CrfGradArgs& A, const int bx
     __shared__ float s_max[NW];
     const int K = crf.K;
     for (int i = threadIdx.x; i < K - 1; i += NW * 64) s_tab64[i] = 0ull;
-    crf.dt = exposure[0];
     const bool blur_hdr = (flags & HS_FLAG_BLUR_HDR) && N > 1;
     const float gs = blur_hdr ? 1.f : 1.f / (float)N;
     const float scale = (float)(K - 1) / (crf.umax - crf.umin);
-    const int plane = plane_in;              // pose * 3 + ch
+    const int plane = plane_in;              // pose * 3 + ch; radiance-domain blur: frame * 3 + ch (the frame's mean plane)
     const int pose = plane / 3, ch = plane - 3 * pose;
-    const float* Hp = pose_hdr + ((int64_t)(blur_hdr ? N : pose) * 3 + ch) * HW;
-    const float* gp = dL_dcolor + (int64_t)ch * HW;
+    const int frame = blur_hdr ? pose : (A.F > 1 ? pose / N : 0);
+    crf.dt = exposure[frame];
+    const float* Hp = pose_hdr + ((int64_t)(blur_hdr ? A.F * N + frame : pose) * 3 + ch) * HW;
+    const float* gp = dL_dcolor + ((int64_t)frame * 3 + ch) * HW;
     const float* t = crf.table + ch * K;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
@@ -860,7 +868,7 @@ __device__ __forceinline__ void crf_grad_body(const CrfGradArgs& A, const int bx
 }
 
 struct RenderBwd {
-    int W, H, gx, gy, ntiles, N, flags;
+    int W, H, gx, gy, ntiles, N, F, flags;   // N: poses per FRAME, F: frames (the launch covers F x N poses)
     const uint2* ranges; const uint32_t* point_list; const float4* rec; const float* bg;
     const float* final_T; const uint32_t* n_contrib; const float* pose_hdr;
     const float* dL_dcolor; const float* dL_dhdr; const float* dL_dalpha; const float* dL_dinvdepth;
@@ -878,20 +886,22 @@ struct RenderBwd {
     CrfGradArgs crf_tail;          // ... take 2048-pixel blocks of the CRF gradient's first stage (bx * planes of them)
 };
 
-// Upstream gradient w.r.t. this pose's radiance H_ch at one pixel (the HDR prologue).
-__device__ __forceinline__ float pixel_grad(const RenderBwd& p, const Crf& c, int pose, int ch, int64_t pix, int64_t HW) {
+// Upstream gradient w.r.t. this pose's radiance H_ch at one pixel (the HDR prologue).  `frame`: the frame the pose belongs
+// to -- its image's gradient planes, its mean-radiance slot; 1 / N is the frame's N.
+__device__ __forceinline__ float pixel_grad(const RenderBwd& p, const Crf& c, int pose, int frame, int ch, int64_t pix, int64_t HW) {
     const float invN = 1.f / (float)p.N;
-    float g = p.dL_dcolor[ch * HW + pix];
+    const int64_t gpl = ((int64_t)frame * 3 + ch) * HW + pix;
+    float g = p.dL_dcolor[gpl];
     if (!(p.flags & HS_FLAG_HDR)) return g * invN;
     float out = 0.f;
     if (p.N == 1 || !(p.flags & HS_FLAG_BLUR_HDR)) {
         const float Hv = p.pose_hdr[((int64_t)pose * 3 + ch) * HW + pix];
         out = crf_grad_H(c, ch, Hv, g * invN);
     } else {
-        const float Hm = p.pose_hdr[((int64_t)p.N * 3 + ch) * HW + pix];
+        const float Hm = p.pose_hdr[((int64_t)(p.F * p.N + frame) * 3 + ch) * HW + pix];
         out = crf_grad_H(c, ch, Hm, g) * invN;
     }
-    if (p.dL_dhdr) out += p.dL_dhdr[ch * HW + pix] * invN;
+    if (p.dL_dhdr) out += p.dL_dhdr[gpl] * invN;
     return out;
 }
 
@@ -911,7 +921,7 @@ struct PixB {
     uint32_t last;
 };
 
-__device__ __forceinline__ void load_pixel_bwd(const RenderBwd& p, PixB& s, bool inside, int pose, int px, int py) {
+__device__ __forceinline__ void load_pixel_bwd(const RenderBwd& p, PixB& s, bool inside, int pose, int frame, int px, int py) {
     const int64_t HW = (int64_t)p.H * p.W;
     const int64_t pix = (int64_t)py * p.W + px;
     s.T = 0.f; s.dL0 = s.dL1 = s.dL2 = 0.f; s.last = 0;
@@ -919,13 +929,14 @@ __device__ __forceinline__ void load_pixel_bwd(const RenderBwd& p, PixB& s, bool
         s.T = p.final_T[(int64_t)pose * HW + pix];
         s.last = p.n_contrib[(int64_t)pose * HW + pix];
         Crf c = p.crf;
-        if (p.flags & HS_FLAG_HDR) c.dt = p.exposure[0];
-        s.dL0 = pixel_grad(p, c, pose, 0, pix, HW);
-        s.dL1 = pixel_grad(p, c, pose, 1, pix, HW);
-        s.dL2 = pixel_grad(p, c, pose, 2, pix, HW);
+        if (p.flags & HS_FLAG_HDR) c.dt = p.exposure[frame];
+        s.dL0 = pixel_grad(p, c, pose, frame, 0, pix, HW);
+        s.dL1 = pixel_grad(p, c, pose, frame, 1, pix, HW);
+        s.dL2 = pixel_grad(p, c, pose, frame, 2, pix, HW);
     }
     float bg_dot = (p.bg[0] * s.dL0 + p.bg[1] * s.dL1) + p.bg[2] * s.dL2;
     // accumulated opacity A = 1 - T_final: dA/dalpha_i = T_final / (1 - alpha_i), the background term with sign flipped
+    // (dL_dalpha / dL_dinvdepth: per-image gradients, never given together with frames -- hs_backward refuses them)
     if (p.dL_dalpha && inside) bg_dot -= p.dL_dalpha[pix] / (float)p.N;
     s.q = bg_dot;
     s.dLd = (p.dL_dinvdepth && inside) ? p.dL_dinvdepth[pix] / (float)p.N : 0.f;
@@ -1063,8 +1074,9 @@ render_bwd_kernel(RenderBwd p) {
     {
         const int qx = sx + (lane & 15), qy0 = sy + 2 * (lane >> 4);
         PixB t0, t1;
-        load_pixel_bwd(p, t0, qx < p.W && qy0 < p.H, pose, qx, qy0);
-        load_pixel_bwd(p, t1, qx < p.W && qy0 + 1 < p.H, pose, qx, qy0 + 1);
+        const int frame = p.F > 1 ? pose / p.N : 0;   // (uniform; once per tile, in the prologue)
+        load_pixel_bwd(p, t0, qx < p.W && qy0 < p.H, pose, frame, qx, qy0);
+        load_pixel_bwd(p, t1, qx < p.W && qy0 + 1 < p.H, pose, frame, qx, qy0 + 1);
         float* const o = s_ent + wave * (7 * 128);
         const int r0 = (qy0 - sy) * 16 + (lane & 15), r1 = r0 + 16;
         o[r0] = t0.T; o[r1] = t1.T;
@@ -1310,13 +1322,14 @@ int launch_render_fwd(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, u
     RenderFwd p;
     p.W = d.W; p.H = d.H; p.gx = (d.W + kTile - 1) / kTile;
     const int gy = (d.H + kTile - 1) / kTile;
-    p.ntiles = p.gx * gy; p.N = d.n_poses; p.flags = a.flags;
+    const int F = frames_of(d);
+    p.ntiles = p.gx * gy; p.N = d.n_poses / F; p.flags = a.flags;
     char* bin = (char*)a.binning; char* img = (char*)a.image; char* geom = (char*)a.geom;
     p.ranges = (const uint2*)(bin + L.ranges); p.point_list = (const uint32_t*)(bin + L.point_list);
     p.rec = (const float4*)(geom + L.rec); p.bg = a.bg;
     p.out_color = a.out_color; p.out_hdr = a.out_hdr;
     p.final_T = (float*)(img + L.final_T); p.n_contrib = (uint32_t*)(img + L.n_contrib);
-    const bool need_pose = (a.flags & HS_FLAG_HDR) || d.n_poses > 1;
+    const bool need_pose = (a.flags & HS_FLAG_HDR) || p.N > 1;
     p.pose_hdr = need_pose ? (float*)(img + L.pose_hdr) : nullptr;
     p.crf.table = a.crf_table; p.crf.K = a.crf_K; p.crf.umin = a.crf_umin; p.crf.umax = a.crf_umax; p.crf.dt = 1.f;
     p.exposure = a.exposure;
@@ -1336,10 +1349,10 @@ int launch_render_fwd(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, u
         order_tiles_kernel<<<8, 1024, 0, s>>>(grid, p.gx, n_static, p.tile_work, (uint32_t*)(img + L.tile_order));
         HS_LAUNCH_CHECK();
     }
-    if (d.n_poses > 1) {
+    if (p.N > 1) {
         const int64_t HW = (int64_t)d.W * d.H;
-        resolve_kernel<<<ceil_div(3 * HW, 256), 256, 0, s>>>(HW, d.n_poses, a.flags, p.pose_hdr, p.crf, a.exposure,
-                                                            a.out_color, a.out_hdr);
+        resolve_kernel<<<ceil_div((int64_t)F * 3 * HW, 256), 256, 0, s>>>(HW, p.N, F, a.flags, p.pose_hdr, p.crf, a.exposure,
+                                                                         a.out_color, a.out_hdr);
         HS_LAUNCH_CHECK();
     }
     return HS_OK;
@@ -1349,12 +1362,12 @@ static bool crf_grad_args(const hs_bwd_args& a, const hs_layout& L, CrfGradArgs&
     const hs_dims& d = a.dims;
     if (!((a.flags & HS_FLAG_HDR) && (a.dL_dcrf_table || a.dL_dexposure))) return false;
     A.crf.table = a.crf_table; A.crf.K = a.crf_K; A.crf.umin = a.crf_umin; A.crf.umax = a.crf_umax; A.crf.dt = 1.f;
-    A.HW = (int64_t)d.W * d.H; A.N = d.n_poses; A.flags = a.flags;
+    A.HW = (int64_t)d.W * d.H; A.F = frames_of(d); A.N = d.n_poses / A.F; A.flags = a.flags;
     A.partials = (float*)((char*)a.bwd + L.crf_partials);
     A.pose_hdr = (const float*)((const char*)a.image + L.pose_hdr);
     A.exposure = a.exposure; A.dL_dcolor = a.dL_dout_color;
-    const bool blur_hdr = (a.flags & HS_FLAG_BLUR_HDR) && d.n_poses > 1;
-    A.planes = 3 * (blur_hdr ? 1 : d.n_poses);
+    const bool blur_hdr = (a.flags & HS_FLAG_BLUR_HDR) && A.N > 1;
+    A.planes = 3 * (blur_hdr ? A.F : d.n_poses);   // frame-major either way
     A.bx = ceil_div(A.HW, (int64_t)waves * kCrfPixPerWave);
     return true;
 }
@@ -1366,7 +1379,8 @@ int launch_crf_bwd(const hs_bwd_args& a, const hs_layout& L, hipStream_t s, CrfR
         crf_grad_kernel<<<dim3(A.bx, A.planes), 256, (size_t)(a.crf_K - 1) * sizeof(unsigned long long), s>>>(A);
     CrfReduce cr;
     cr.partials = A.partials; cr.bx = A.bx; cr.planes = A.planes; cr.K = a.crf_K; cr.d_table = a.dL_dcrf_table;
-    cr.d_exposure = a.dL_dexposure; cr.nblocks = ceil_div(3 * a.crf_K + 1, 4);
+    cr.F = A.F;
+    cr.d_exposure = a.dL_dexposure; cr.nblocks = ceil_div(3 * a.crf_K + cr.F, 4);
     if (defer) *defer = cr;   // a later launch of the call adds the rows up (its first workgroups): one launch less
     else crf_reduce_kernel<<<cr.nblocks, 256, 0, s>>>(cr);
     HS_LAUNCH_CHECK();
@@ -1378,7 +1392,8 @@ int launch_render_bwd(const hs_bwd_args& a, const hs_layout& L, hipStream_t s, u
     const hs_dims& d = a.dims;
     RenderBwd p;
     p.W = d.W; p.H = d.H; p.gx = (d.W + kTile - 1) / kTile; p.gy = (d.H + kTile - 1) / kTile;
-    p.ntiles = p.gx * p.gy; p.N = d.n_poses; p.flags = a.flags;
+    p.F = frames_of(d);
+    p.ntiles = p.gx * p.gy; p.N = d.n_poses / p.F; p.flags = a.flags;
     const char* bin = (const char*)a.binning; const char* img = (const char*)a.image; const char* geom = (const char*)a.geom;
     p.ranges = (const uint2*)(bin + L.ranges); p.point_list = (const uint32_t*)(bin + L.point_list);
     p.rec = (const float4*)(geom + L.rec); p.bg = a.bg;

@@ -262,7 +262,8 @@ def projection_matrix(tanfovx: float, tanfovy: float, znear: float = 0.01, zfar:
 
 
 class HDRBlurFormation(nn.Module):
-    """B_i = mean_k F_theta(dt_i * H(G, T_i(t_k))) -- one rasterizer call per captured frame."""
+    """B_i = mean_k F_theta(dt_i * H(G, T_i(t_k))) -- one rasterizer call per captured frame (`forward`), or one call for
+    several frames together (`forward_frames`)."""
 
     def __init__(self, trajectory: TrajectorySpline, n_frames: int, W: int, H: int, tanfovx: float, tanfovy: float,
                  n_virtual: int = 8, crf: Optional[ImplicitCRF] = None, blur_domain: str = "ldr", sh_degree: int = 3,
@@ -345,6 +346,35 @@ class HDRBlurFormation(nn.Module):
         per_frame = getattr(self._factory, "for_frame", None)     # (FrameRasterizers: one persistent rasterizer per frame)
         rast = per_frame(i, settings) if per_frame is not None else self._factory(settings)
         ldr, radii, hdr = rast(means3D, means2D, opacities, shs=shs, scales=scales, rotations=rotations)
+        return ldr, hdr, radii, means2D
+
+    def forward_frames(self, frame_ids, means3D, opacities, shs, scales, rotations, bg=None, cameras=None):
+        """The captured frames `frame_ids` (a sequence of frame indices) in ONE rasterizer call (settings.n_frames = F = their
+        number): the cameras are the frames' slices of cameras_all() (or of `cameras`, its result), the exposures
+        exp(log_exposure[frame_ids]).  Returns (ldr [F,3,H,W], hdr [F,3,H,W], radii [P], means2D) -- ldr[k] / hdr[k] are bit
+        for bit what forward(frame_ids[k], ...) returns, radii is the maximum and means2D.grad the sum over the frames."""
+        ids = [int(i) for i in frame_ids]
+        F, n_all = len(ids), self.log_exposure.shape[0]
+        if F < 1 or any(i < 0 or i >= n_all for i in ids):
+            raise ValueError(f"forward_frames: frame_ids {ids} must name at least one of the {n_all} frames")
+        V, PV, Cp = self.cameras_all() if cameras is None else cameras
+        exposure = torch.exp(self.log_exposure)
+        if ids != list(range(n_all)):          # (all frames in order: no gather at all)
+            index = torch.tensor(ids, dtype=torch.long, device=self.log_exposure.device)
+            V, PV, Cp, exposure = V.index_select(0, index), PV.index_select(0, index), Cp.index_select(0, index), exposure.index_select(0, index)
+        dev = means3D.device
+        bg = torch.zeros(3, device=dev) if bg is None else bg
+        settings = GaussianRasterizationSettings(
+            image_height=self.H, image_width=self.W, tanfovx=self.tanfovx, tanfovy=self.tanfovy, bg=bg,
+            scale_modifier=1.0, viewmatrix=V[0, 0], projmatrix=PV[0, 0], sh_degree=self.sh_degree, campos=Cp[0, 0],
+            prefiltered=False, debug=False, exposure=exposure, crf_table=self.crf.table(),
+            crf_range=self.crf.u_range, viewmatrices=V, projmatrices=PV, camposes=Cp, blur_domain=self.blur_domain,
+            n_frames=F)
+        means2D = torch.zeros_like(means3D, requires_grad=means3D.requires_grad)
+        rast = self._factory(settings)
+        ldr, radii, hdr = rast(means3D, means2D, opacities, shs=shs, scales=scales, rotations=rotations)
+        if F == 1:                             # (n_frames = 1 is the call without frames: [3,H,W] images)
+            ldr, hdr = ldr[None], hdr[None]
         return ldr, hdr, radii, means2D
 
 

@@ -20,6 +20,11 @@ H --(exposure, shared CRF)--> I --(average over virtual poses)--> B; Readme.md:5
 settings fields `exposure`, `crf_table`, `crf_range`, `viewmatrices/projmatrices/camposes`
 (N virtual poses) and `blur_domain`.  With `crf_table` set, forward returns (ldr, radii, hdr).
 
+Frames: `n_frames = F > 1` groups the F * N poses of `viewmatrices` ... into F consecutive runs of N, each a captured frame
+with its own `exposure[f]` and its own output image -- one training step over F frames (or a mini-batch of F plain views,
+N = 1) in ONE call: forward returns (color [F,3,H,W], radii) / (ldr [F,3,H,W], radii, hdr [F,3,H,W]), frame f's images bit
+for bit those of a call on its poses alone, and one backward writes every Gaussian's gradient row once.
+
 All compute happens in libhdrsplat.so (hand-written HIP for gfx950) through the C ABI of
 include/hdrsplat.h; PyTorch only owns memory and streams.  There is no fallback path.
 """
@@ -63,6 +68,32 @@ class GaussianRasterizationSettings(NamedTuple):
     # how the SH sum s becomes the Gaussian's linear radiance: "relu_shift" = max(s + 0.5, 0) (the published rule),
     # "exp" = e^s, "softplus" = ln(1 + e^s) (an HDR scene wants an unbounded, positive radiance)
     radiance_activation: str = "relu_shift"
+    # frames of the call: viewmatrices / projmatrices / camposes hold n_frames consecutive runs of N poses ([F*N,...] or
+    # [F,N,...]), exposure is [n_frames], and every image output gains a leading dimension [n_frames]; 1 = no frames
+    n_frames: int = 1
+
+
+def frames_of(settings) -> int:
+    """The frames a call with `settings` renders (1: the call without frames), after checking what can be checked without a
+    GPU: ValueError when n_frames does not divide the poses or the exposure is not one value per frame."""
+    F = int(getattr(settings, "n_frames", 1) or 1)
+    if F < 1:
+        raise ValueError(f"n_frames must be >= 1, got {F}")
+    if F == 1:
+        return 1
+    poses = []
+    for name in ("viewmatrices", "projmatrices", "camposes"):
+        t = getattr(settings, name)
+        if t is None:
+            raise ValueError(f"n_frames={F} needs viewmatrices, projmatrices and camposes ([F*N,...] or [F,N,...])")
+        poses.append(t.numel() // (3 if name == "camposes" else 16))
+    if len(set(poses)) != 1:
+        raise ValueError("viewmatrices, projmatrices and camposes must hold the same number of poses")
+    if poses[0] < F or poses[0] % F:
+        raise ValueError(f"{poses[0]} poses cannot be grouped into n_frames={F} frames of equally many poses")
+    if settings.crf_table is not None and settings.exposure is not None and settings.exposure.numel() != F:
+        raise ValueError(f"exposure must hold one value per frame ({F}), got {settings.exposure.numel()}")
+    return F
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -277,9 +308,10 @@ def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, sh
         views = _f32c(settings.viewmatrix, dev).reshape(1, 16)
         projs = _f32c(settings.projmatrix, dev).reshape(1, 16)
         campos = _f32c(settings.campos, dev).reshape(1, 3)
-    N = views.shape[0]
+    N = views.shape[0]     # all poses of the call: F frames of N / F
     if projs.shape[0] != N or campos.shape[0] != N:
         raise ValueError("viewmatrices, projmatrices and camposes must have the same leading dimension")
+    F = frames_of(settings)
     bg = _f32c(settings.bg, dev).reshape(3)
     M = shs.shape[1] if shs is not None else 0
     hdr = crf_table is not None
@@ -287,7 +319,7 @@ def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, sh
     if hdr:
         flags |= L.HS_FLAG_HDR
         if exposure is None:
-            exposure = torch.ones((), device=dev)
+            exposure = torch.ones(F, device=dev)
         if settings.blur_domain == "hdr":
             flags |= L.HS_FLAG_BLUR_HDR
         elif settings.blur_domain != "ldr":
@@ -303,15 +335,17 @@ def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, sh
         flags |= L.HS_FLAG_RADIANCE_SOFTPLUS
     elif act != "relu_shift":
         raise ValueError("radiance_activation must be 'relu_shift', 'exp' or 'softplus'")
-    exposure = None if exposure is None else _f32c(exposure, dev).reshape(1)
+    exposure = None if exposure is None else _f32c(exposure, dev).reshape(F)
     crf_table = _f32c(crf_table, dev)
     crf_K = int(crf_table.shape[1]) if hdr else 0
 
     sync_mode = capacity is None
-    dims, sizes, layout = L.plan(P, M, int(settings.sh_degree), W, H, N, 0 if sync_mode else int(capacity), crf_K)
+    n_frames = F if F > 1 else 0     # (hs_dims.n_frames: 0 = the call without frames)
+    dims, sizes, layout = L.plan(P, M, int(settings.sh_degree), W, H, N, 0 if sync_mode else int(capacity), crf_K, n_frames)
     geom = _empty(max(int(sizes.geom_bytes), 256), torch.uint8, dev, "geom")
-    out_color = _empty((3, H, W), torch.float32, dev, "out_color")
-    out_hdr = _empty((3, H, W), torch.float32, dev, "out_hdr") if hdr else None
+    img_shape = (F, 3, H, W) if F > 1 else (3, H, W)
+    out_color = _empty(img_shape, torch.float32, dev, "out_color")
+    out_hdr = _empty(img_shape, torch.float32, dev, "out_hdr") if hdr else None
     radii = _empty(P, torch.int32, dev, "radii")
     invdepth = _empty((N, H, W), torch.float32, dev, "invdepth") if want_invdepth else None
 
@@ -336,7 +370,7 @@ def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, sh
         a.stages = L.HS_STAGE_PREPROCESS
         L.forward(a, stream, "hs_forward[preprocess]")
         R = int(geom[:4].view(torch.int32).item()) & 0xFFFFFFFF if P > 0 else 0
-        dims, sizes, layout = L.plan(P, M, int(settings.sh_degree), W, H, N, R, crf_K)
+        dims, sizes, layout = L.plan(P, M, int(settings.sh_degree), W, H, N, R, crf_K, n_frames)
         a.dims = dims
         a.stages = L.HS_STAGE_BIN | L.HS_STAGE_RENDER
     else:
@@ -517,7 +551,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         saved = ctx.saved_tensors
         dev = saved[0].device
         if grad_color is None:  # the loss used only the other outputs
-            grad_color = torch.zeros(3, st.H, st.W, dtype=torch.float32, device=dev)
+            shape = (st.dims.n_frames, 3, st.H, st.W) if st.dims.n_frames > 1 else (3, st.H, st.W)
+            grad_color = torch.zeros(shape, dtype=torch.float32, device=dev)
         gcol = _f32c(grad_color, dev)
         ghdr = _f32c(grad_hdr, dev) if grad_hdr is not None else None
         galpha = _f32c(grad_alpha, dev) if grad_alpha is not None else None
@@ -601,14 +636,15 @@ def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bo
     m3, op, shs, cp, sc, ro, cv, exp_t, crf_t = saved
     dev = m3.device
     P, M = st.dims.P, st.dims.M
-    _, sizes, _ = L.plan(P, M, st.dims.sh_degree, st.W, st.H, st.dims.n_poses, st.dims.capacity, st.dims.crf_K)
+    _, sizes, _ = L.plan(P, M, st.dims.sh_degree, st.W, st.H, st.dims.n_poses, st.dims.capacity, st.dims.crf_K,
+                         st.dims.n_frames)
     bwd = _empty(max(int(sizes.bwd_bytes), 256), torch.uint8, dev, "bwd")
     hdr = bool(st.flags & L.HS_FLAG_HDR)
     # (the SH rows -- four fifths of the bytes at degree 3 -- come last of the summed span, so a chunked exchange moves the
     # other per-Gaussian rows as a few short slices and the SH rows of a chunk as ONE long one)
     spec = [("means3D", (P, 3), True), ("opacities", (P, 1), True), ("colors_precomp", (P, 3), cp is not None),
             ("scales", (P, 3), sc is not None), ("rotations", (P, 4), ro is not None),
-            ("cov3D_precomp", (P, 6), cv is not None), ("exposure", (1,), hdr), ("crf_table", (3, st.crf_K), hdr),
+            ("cov3D_precomp", (P, 6), cv is not None), ("exposure", (max(st.dims.n_frames, 1),), hdr), ("crf_table", (3, st.crf_K), hdr),
             ("shs", (P, M, 3), shs is not None and not defer_sh),
             ("means2D", (P, 3), True),
             ("viewmatrices", (st.dims.n_poses, 16), want_pose), ("projmatrices", (st.dims.n_poses, 16), want_pose),
@@ -914,6 +950,9 @@ class GaussianRasterizer(nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+        if frames_of(rs) > 1 and (self.return_alpha or self.return_invdepth):
+            raise ValueError("return_alpha / return_invdepth are per-image outputs and are not supported with n_frames > 1: "
+                             "render those frames one call each")
         given = [t for t in (means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
                              rs.exposure, rs.crf_table, rs.viewmatrix, rs.projmatrix, rs.campos, rs.viewmatrices,
                              rs.projmatrices, rs.camposes) if isinstance(t, torch.Tensor)]
@@ -1000,10 +1039,12 @@ def inspect_state(out_tensor) -> dict:
     # the published sort key (tile << 32) | depth_bits, rebuilt from the two halves the split sort keeps
     dbits = depths.view(torch.int32).to(torch.int64)[pl.to(torch.int64)] & 0xFFFFFFFF
     keys_sorted = (tile_sorted << 32) | dbits
-    # per-pose radiance images the CRF / blur average read (slot N: the pose mean, when N > 1); None when not kept
-    n_img = d.n_poses + (1 if d.n_poses > 1 else 0)
+    # per-pose radiance images the CRF / blur average read (then, with N > 1 poses per frame, one pose mean per frame: slot
+    # n_poses + f; without frames: slot N); None when not kept
+    F = max(d.n_frames, 1)
+    n_img = d.n_poses + (F if d.n_poses // F > 1 else 0)
     pose_hdr = (view(st.image, lay.pose_hdr, n_img * 3 * d.W * d.H, torch.float32).reshape(n_img, 3, d.H, d.W)
-                if ((st.flags & L.HS_FLAG_HDR) or d.n_poses > 1) else None)
+                if ((st.flags & L.HS_FLAG_HDR) or d.n_poses // F > 1) else None)
     # (st.keep as _run_forward fills it)
     _, _, _, kept_opacities, _, _, kept_scales, kept_rotations, _ = st.keep
     return dict(

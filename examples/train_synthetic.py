@@ -12,6 +12,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --lambda-dssim 0.2     # the published L1 + D-SSIM loss, fused
     python examples/train_synthetic.py --steps 300 --fused-adam           # the update through optim.GaussianAdam, visible rows only
     python examples/train_synthetic.py --steps 300 --fused-adam --raw     # the stored (logit) opacities go straight into the rasterizer
+    python examples/train_synthetic.py --steps 300 --batch-frames         # all frames of a step in ONE rasterizer call
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -57,7 +58,7 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
-        graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False):
+        graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -66,7 +67,13 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     stays outside the captured step.
     raw: the learner's rasterizers take the cloud as it is STORED (GaussianRasterizer(..., parameterization="raw")): the
     logit opacities go in as the leaf they are -- no torch.sigmoid in front, their gradient a view of the rasterizer's flat
-    buffer -- and the fixed scales / rotations as logs / quaternions."""
+    buffer -- and the fixed scales / rotations as logs / quaternions.
+    batch_frames: the step is ONE rasterizer call over all frames (HDRBlurFormation.forward_frames, settings.n_frames) and
+    one loss call over the [frames, 3, H, W] batch instead of a call per frame: the same gradients up to fp32 summation
+    order.  Eager only: together with graph=True it raises (the captured step keeps one rasterizer per frame)."""
+    if batch_frames and graph:
+        raise ValueError("batch_frames=True (--batch-frames) is not supported together with graph=True (--graph): the captured "
+                         "step is built around one persistent rasterizer per frame (image_formation.FrameRasterizers)")
     dev = torch.device(device)
     sc = S.make_scene(P, W, H, deg, seed=seed, hdr=True)
     cam = sc.camera
@@ -150,7 +157,29 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         torch.stack(losses).sum().backward()
         return torch.stack([l_.detach() for l_ in losses]), torch.stack(mses)
 
-    step_fn = gradients
+    target_batch = torch.stack(targets) if batch_frames else None
+
+    def gradients_batched():
+        """The same step as ONE rasterizer call over all frames and one backward; returns (losses, per-frame MSE) with
+        losses.sum() the step's loss: per frame for the plain L1, ONE entry for the fused L1 + D-SSIM loss (a single loss call
+        over the batch has no per-frame values)."""
+        for p_ in learn:
+            p_.grad = None
+        opac = raw_opac if raw else torch.sigmoid(raw_opac)
+        ldr, _, radii, _ = model.forward_frames(range(frames), fixed["means3D"], opac, shs, fixed["scales"], fixed["rotations"])
+        if fused_adam:
+            torch.gt(radii, 0, out=seen)      # (radii: the maximum over every frame's poses)
+        if lambda_dssim > 0:
+            # (one fused loss over the [frames, 3, H, W] batch: it averages over every plane, i.e. it is the MEAN of the
+            # per-frame losses; the step's loss is their sum)
+            losses = (photometric_loss(ldr, target_batch, lambda_dssim) * frames).reshape(1)
+        else:
+            losses = torch.stack([mean_by_rows((ldr[i] - targets[i]).abs()) for i in range(frames)])
+        mses = torch.stack([mean_by_rows((ldr[i].detach() - targets[i]) ** 2) for i in range(frames)])
+        losses.sum().backward()
+        return losses.detach(), mses
+
+    step_fn = gradients_batched if batch_frames else gradients
     if graph:
         gradients()                                   # (creates the per-frame rasterizers)
         captured = GraphedStep(gradients, per_frame.rasterizers(frames), params=learn)
@@ -204,9 +233,12 @@ def main(argv=None):
     ap.add_argument("--raw", action="store_true",
                     help="pass the stored (logit) opacities to GaussianRasterizer(..., parameterization='raw') instead of "
                          "torch.sigmoid in front of the default rasterizer")
+    ap.add_argument("--batch-frames", action="store_true",
+                    help="render all frames of a step in ONE rasterizer call (settings.n_frames; HDRBlurFormation.forward_frames) "
+                         "instead of one call per frame; eager only (not with --graph)")
     a = ap.parse_args(argv)
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
-            fused_adam=a.fused_adam, raw=a.raw)
+            fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

@@ -22,6 +22,13 @@
  * "Instance" below means one (pose, Gaussian) pair: with n_poses = N the library renders N
  * virtual sharp images in one launch (pose id folded into the tile sort key) and averages
  * them (motion blur as N-pose render averaging, /root/reference/assets/pipeline.png "+").
+ *
+ * Frames (detected by name: hs_max_frames).  hs_dims.n_frames = F > 1 groups the n_poses = F * N poses of a call into F
+ * consecutive runs of N: frame f owns the poses f * N .. f * N + N - 1, has its own exposure[f] and its own output image --
+ * one training step over F captured frames (or a mini-batch of F plain views, N = 1) in ONE call.  Everything per pose stays
+ * per pose, everything per Gaussian is summed (radii: maximised) over all F * N poses; what becomes per frame is noted next
+ * to each field below.  Frame f's images carry the bits a separate call on its N poses gives.  n_frames = 0 or 1 is the
+ * call without frames: the same workspace sizes and offsets, the same kernels, the same outputs.
  */
 #ifndef HDRSPLAT_H
 #define HDRSPLAT_H
@@ -104,7 +111,10 @@ typedef struct hs_dims {
     int64_t capacity;  /* binning capacity in (tile, instance) pairs */
     int32_t crf_K;     /* knots per channel of the CRF table, 0 when the call has no HDR tone-map: sizes the scratch of
                           the CRF-gradient stage (must equal hs_fwd_args.crf_K / hs_bwd_args.crf_K under HS_FLAG_HDR) */
-    int32_t reserved;  /* 0 */
+    int32_t n_frames;  /* F: the poses form F consecutive runs of n_poses / F, each with its own exposure and output image;
+                          0 means 1 (a zero-initialised struct is the call without frames).  HS_EINVAL when negative, larger
+                          than n_poses, or not a divisor of n_poses.  (This field was `reserved`, 0, before hs_max_frames
+                          existed: a library without that export ignores it) */
 } hs_dims;
 
 typedef struct hs_sizes {
@@ -146,18 +156,18 @@ typedef struct hs_fwd_args {
     const float* scales;         /* [P,3] or NULL */
     const float* rotations;      /* [P,4] (w,x,y,z) or NULL */
     const float* cov3D_precomp;  /* [P,6] or NULL */
-    const float* exposure;       /* [1] (HDR) or NULL */
+    const float* exposure;       /* [F] (HDR; F = max(n_frames, 1): one exposure time per frame) or NULL */
     const float* crf_table;      /* [3,crf_K] (HDR) or NULL */
     /* caller-owned workspaces, sizes from hs_plan(), 256-byte aligned */
     void* geom;
     void* binning;
     void* image;
     /* device outputs */
-    float* out_color;            /* [3,H,W]; LDR when HS_FLAG_HDR */
-    float* out_hdr;              /* [3,H,W] linear radiance (HDR) or NULL */
-    int32_t* radii;              /* [P] max over poses */
-    float* out_invdepth;         /* [N,H,W] or NULL: expected inverse depth sum_i alpha_i T_i / z_i per pose
-                                    (the caller averages the poses) */
+    float* out_color;            /* [F,3,H,W] (one image per frame); LDR when HS_FLAG_HDR */
+    float* out_hdr;              /* [F,3,H,W] linear radiance (HDR) or NULL */
+    int32_t* radii;              /* [P] max over ALL poses of the call (every frame's) */
+    float* out_invdepth;         /* [n_poses,H,W] or NULL: expected inverse depth sum_i alpha_i T_i / z_i per pose
+                                    (the caller averages the poses); per pose, whatever n_frames is */
     void* counters_host;         /* (HS_VERSION 304) NULL, or a host address the GPU can write (page-locked, mapped: what
                                     hipHostMalloc / torch pin_memory return): HS_STAGE_BIN leaves a copy of hs_counters
                                     (32 bytes) there -- written by its last kernel, so a sync-free caller that wants to
@@ -200,7 +210,7 @@ typedef struct hs_bwd_args {
     const float* scales;
     const float* rotations;
     const float* cov3D_precomp;
-    const float* exposure;
+    const float* exposure;        /* [F], as in the forward */
     const float* crf_table;
     /* state produced by hs_forward (same buffers) */
     const void* geom;
@@ -208,34 +218,39 @@ typedef struct hs_bwd_args {
     const void* image;
     void* bwd;                    /* scratch, hs_sizes.bwd_bytes */
     /* upstream gradients */
-    const float* dL_dout_color;   /* [3,H,W] */
-    const float* dL_dout_hdr;     /* [3,H,W] or NULL */
-    const float* dL_dout_alpha;   /* [H,W] or NULL: gradient w.r.t. the accumulated-opacity image 1 - mean_k final_T_k */
+    const float* dL_dout_color;   /* [F,3,H,W] */
+    const float* dL_dout_hdr;     /* [F,3,H,W] or NULL */
+    const float* dL_dout_alpha;   /* [H,W] or NULL: gradient w.r.t. the accumulated-opacity image 1 - mean_k final_T_k
+                                     (a per-image gradient: HS_EINVAL together with n_frames > 1) */
     /* outputs (each may be NULL when its input is absent) */
     float* dL_dmeans3D;           /* [P,3] */
-    float* dL_dmeans2D;           /* [P,3] screen-space gradient (NDC-scaled), summed over poses */
+    float* dL_dmeans2D;           /* [P,3] screen-space gradient (NDC-scaled), summed over ALL poses of the call; like it,
+                                     every per-Gaussian gradient below is the sum over every frame's poses */
     float* dL_dopacities;         /* [P] */
     float* dL_dshs;               /* [P,M,3] */
     float* dL_dcolors_precomp;    /* [P,3] */
     float* dL_dscales;            /* [P,3] */
     float* dL_drotations;         /* [P,4] */
     float* dL_dcov3D_precomp;     /* [P,6] */
-    float* dL_dexposure;          /* [1] (HDR) */
-    float* dL_dcrf_table;         /* [3,crf_K] (HDR) */
+    float* dL_dexposure;          /* [F] (HDR): entry f from frame f's pixels only, bit for bit what a separate call gives */
+    float* dL_dcrf_table;         /* [3,crf_K] (HDR), summed over the frames in a fixed order (frame-major) */
     /* camera-pose gradients (the reference optimises camera motion jointly, Readme.md:54);
      * all three or none; same flat transposed layout as the inputs, unused entries are zero */
-    float* dL_dviewmatrices;      /* [N,16] or NULL */
-    float* dL_dprojmatrices;      /* [N,16] or NULL */
-    float* dL_dcamposes;          /* [N,3]  or NULL */
+    float* dL_dviewmatrices;      /* [n_poses,16] or NULL (per pose, whatever n_frames is) */
+    float* dL_dprojmatrices;      /* [n_poses,16] or NULL */
+    float* dL_dcamposes;          /* [n_poses,3]  or NULL */
     /* view-parallel exchange: when non-NULL, the colour gradient of every instance AFTER the SH clamp
      * mask (zero for culled instances) is written here, [N,P,3]; dL_dshs may then be NULL, and the SH-coefficient
-     * gradient is formed later from the views of ALL ranks by hs_sh_backward_views */
+     * gradient is formed later from the views of ALL ranks by hs_sh_backward_views (per pose, whatever n_frames is) */
     float* dL_dview_colors;
-    const float* dL_dout_invdepth; /* [H,W] or NULL: gradient w.r.t. the pose-averaged inverse-depth image */
+    const float* dL_dout_invdepth; /* [H,W] or NULL: gradient w.r.t. the pose-averaged inverse-depth image (a per-image
+                                      gradient: HS_EINVAL together with n_frames > 1) */
     /* densification statistics, all three or none; updated IN PLACE for every Gaussian that was
      * rasterized in at least one pose: grad_accum += |dL/dmean2D.xy| (the NDC-scaled gradient returned in
      * dL_dmeans2D), denom += 1, max_radii = max(max_radii, radius) -- what a 3DGS trainer keeps between
-     * densification rounds, without re-reading the gradient tensors */
+     * densification rounds, without re-reading the gradient tensors.  With n_frames = F > 1 the call leaves what F calls
+     * leave: for every frame in which the Gaussian was rasterized in at least one pose, grad_accum += |sum over THAT
+     * frame's poses of dL/dmean2D.xy| and denom += 1, frames in ascending order; max_radii takes the maximum over all poses */
     float* densify_grad_accum;    /* [P] */
     float* densify_denom;         /* [P] */
     int32_t* densify_max_radii;   /* [P] */
@@ -272,7 +287,8 @@ typedef struct hs_layout {
      * tile) took the entry -- four bits, one per 8 x 8 block of the 16 x 16 tile.  The render backward walks exactly
      * those entries, one list per block */
     int64_t pair_act;
-    /* image workspace */
+    /* image workspace.  pose_hdr: one [3,H,W] radiance plane per pose (kept under HS_FLAG_HDR or with more than one pose
+     * per frame), followed -- when a frame has N > 1 poses -- by one mean-radiance plane per frame: slot n_poses + f */
     int64_t final_T, n_contrib, pose_hdr;
     /* tile_work: u32 per (pose, tile): (half tile, entry) trips the render forward counted on it = what the render
      * backward will replay; tile_order: u32 per render-backward workgroup: the (pose, tile) it processes (the forward
@@ -303,10 +319,14 @@ typedef struct hs_layout {
 HS_API int hs_version(void);
 HS_API const char* hs_last_error(void);
 /* Limits (HS_EINVAL beyond them): P * n_poses < 2^30 instances, capacity < 2^30 pairs, fewer than 2^22 tiles per pose
- * (a 32768 x 32768 frame), n_poses <= 21845, crf_K <= 4096. */
+ * (a 32768 x 32768 frame), n_poses <= 21845, crf_K <= 4096, 0 <= n_frames <= n_poses with n_poses a multiple of it. */
 HS_API int hs_plan(const hs_dims* dims, hs_sizes* sizes, hs_layout* layout /* may be NULL */);
 HS_API int hs_forward(const hs_fwd_args* args, void* hip_stream);
 HS_API int hs_backward(const hs_bwd_args* args, void* hip_stream);
+/* (detected by name; HS_VERSION unchanged) The largest hs_dims.n_frames this library groups poses into (21845: the limit
+ * on n_poses).  A library WITHOUT this export treats the field as the reserved word it used to be and renders every pose
+ * into one image: a host asks for frames only after it has found the symbol. */
+HS_API int hs_max_frames(void);
 HS_API int hs_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, uint8_t* visible,
                     void* hip_stream);
 
