@@ -47,7 +47,11 @@ __device__ __forceinline__ Dual chain(const Dual& a, double f, double df) { Dual
 __device__ __forceinline__ Dual dsin(const Dual& a) { return chain(a, sin(a.v), cos(a.v)); }
 __device__ __forceinline__ Dual dcos(const Dual& a) { return chain(a, cos(a.v), -sin(a.v)); }
 __device__ __forceinline__ Dual dsqrt(const Dual& a) { const double s = sqrt(a.v); return chain(a, s, 0.5 / s); }
-__device__ __forceinline__ Dual dacos(const Dual& a) { return chain(a, acos(a.v), -1.0 / sqrt(1.0 - a.v * a.v)); }
+__device__ __forceinline__ Dual datan2(const Dual& y, const Dual& x) {
+    Dual r; r.v = atan2(y.v, x.v); const double inv = 1.0 / (x.v * x.v + y.v * y.v);
+    for (int i = 0; i < ND; ++i) r.d[i] = (x.v * y.d[i] - y.v * x.d[i]) * inv;
+    return r;
+}
 
 struct Rigid { Dual R[9]; Dual t[3]; };   // [R t; 0 1]
 
@@ -94,22 +98,24 @@ __device__ void se3_exp(const Dual* xi, Rigid& T) {
     for (int r = 0; r < 3; ++r) T.t[r] = V[3 * r] * rho[0] + V[3 * r + 1] * rho[1] + V[3 * r + 2] * rho[2];
 }
 
-// image_formation.se3_log
+// image_formation.se3_log.  The angle comes from atan2(|vee(R - R^T)| / 2, (tr R - 1) / 2): well conditioned at every angle
+// (an arc-cosine of the trace loses the angle below 5e-4 -- it had to be clamped there, which cost the Jacobian 8e-8 of its
+// scale -- and multiplies the 2^-24 by which float32 knots miss orthonormality by 1 / sin(theta)).
 __device__ void se3_log(const Rigid& T, Dual* xi) {
-    Dual c = 0.5 * ((T.R[0] + T.R[4] + T.R[8]) - mk(1.0));
-    if (c.v > 1.0 - 1e-7) c = mk(1.0 - 1e-7);            // (a clamped value has no derivative: torch.clamp)
-    else if (c.v < -1.0 + 1e-7) c = mk(-1.0 + 1e-7);
-    const Dual th = dacos(c);
-    const bool small = th.v < 1e-4;
+    const Dual v[3] = {T.R[7] - T.R[5], T.R[2] - T.R[6], T.R[3] - T.R[1]};
+    const Dual c = 0.5 * ((T.R[0] + T.R[4] + T.R[8]) - mk(1.0));
+    const Dual sn = dsqrt(1e-30 + 0.25 * (v[0] * v[0] + v[1] * v[1] + v[2] * v[2]));
+    const Dual th = datan2(sn, c);
+    const bool small = th.v < 1e-3;
     const Dual th2 = th * th;
-    const Dual k = small ? (0.5 + (1.0 / 12.0) * th2) : th / (1e-20 + 2.0 * dsin(th));
-    Dual om[3] = {k * (T.R[7] - T.R[5]), k * (T.R[2] - T.R[6]), k * (T.R[3] - T.R[1])};
+    const Dual k = small ? (0.5 + ((1.0 / 12.0) * th2 + (7.0 / 720.0) * (th2 * th2))) : th / (1e-20 + 2.0 * dsin(th));
+    Dual om[3] = {k * v[0], k * v[1], k * v[2]};
     Dual K[9], K2[9];
     hat(om, K);
     mul3(K, K, K2);
     Dual coef;
     if (small) {
-        coef = mk(1.0 / 12.0);
+        coef = 1.0 / 12.0 + (1.0 / 720.0) * th2;
     } else {
         const Dual A = dsin(th) / (1e-20 + th);
         const Dual B = (1.0 - dcos(th)) / (1e-20 + th2);

@@ -206,18 +206,21 @@ def rigid_inv(T: torch.Tensor) -> torch.Tensor:
 
 
 def se3_log(T: torch.Tensor) -> torch.Tensor:
-    """Logarithm SE(3) -> se(3) for rotations well below pi (adjacent video frames); T [..., 4, 4] -> [..., 6]."""
+    """Logarithm SE(3) -> se(3) for rotations well below pi (adjacent video frames); T [..., 4, 4] -> [..., 6].  The angle is
+    atan2(|vee(R - R^T)| / 2, (tr R - 1) / 2): well conditioned at every angle, where an arc-cosine of the trace loses it below
+    5e-4 (and had to be clamped there) and amplifies by 1 / sin(theta) the 2^-24 by which float32 knots miss orthonormality."""
     R, t = T[..., :3, :3], T[..., :3, 3]
-    cos = ((R.diagonal(dim1=-2, dim2=-1).sum(-1) - 1) / 2).clamp(-1 + 1e-7, 1 - 1e-7)
-    th = torch.acos(cos)
-    small = th < 1e-4
-    k = torch.where(small, 0.5 + th * th / 12, th / (2 * torch.sin(th) + 1e-20))
-    om = k[..., None] * torch.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], -1)
-    K = _hat(om)
+    v = torch.stack([R[..., 2, 1] - R[..., 1, 2], R[..., 0, 2] - R[..., 2, 0], R[..., 1, 0] - R[..., 0, 1]], -1)
+    cos = (R.diagonal(dim1=-2, dim2=-1).sum(-1) - 1) / 2
+    th = torch.atan2(torch.sqrt(0.25 * (v * v).sum(-1) + 1e-30), cos)
+    small = th < 1e-3
     th2 = th * th
+    k = torch.where(small, 0.5 + (th2 / 12 + 7.0 / 720 * (th2 * th2)), th / (2 * torch.sin(th) + 1e-20))
+    om = k[..., None] * v
+    K = _hat(om)
     A = torch.where(small, 1 - th2 / 6, torch.sin(th) / (th + 1e-20))
     B = torch.where(small, 0.5 - th2 / 24, (1 - torch.cos(th)) / (th2 + 1e-20))
-    coef = torch.where(small, torch.full_like(th, 1.0 / 12), (1 - A / (2 * B)) / (th2 + 1e-20))
+    coef = torch.where(small, 1.0 / 12 + th2 / 720, (1 - A / (2 * B)) / (th2 + 1e-20))
     Vinv = torch.eye(3, dtype=T.dtype, device=T.device) - 0.5 * K + coef[..., None, None] * _mm(K, K)
     return torch.cat([_mm(Vinv, t[..., None])[..., 0], om], -1)
 
