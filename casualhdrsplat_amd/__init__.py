@@ -4,12 +4,14 @@ Scope: the rasterizer hot path, behind the
 GaussianRasterizer / GaussianRasterizationSettings API, and the fused L1 + D-SSIM training loss
 that consumes its images (losses.photometric_loss, losses.ssim) and the fused, visibility-masked
 Adam step that applies the gradients (optim.GaussianAdam), and the densify / prune of the cloud that
-changes the number of Gaussians under that optimizer (densify.densify_and_prune).  Compute lives in
+changes the number of Gaussians under that optimizer (densify.densify_and_prune), and the neighbour
+distances that size a new cloud (knn.knn_mean_dist2, scene_io.init_from_points).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
 """
 from .densify import DensifyResult, densify_and_prune
+from .knn import knn_mean_dist2
 from .losses import photometric_loss, ssim
 from .optim import GaussianAdam, cloud_param_groups
 from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSettings, GaussianRasterizer,
@@ -17,5 +19,5 @@ from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSet
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats", "BinningOverflow", "SortChainStalled",
            "rasterize_gaussians", "inspect_state", "photometric_loss", "ssim", "GaussianAdam", "cloud_param_groups",
-           "densify_and_prune", "DensifyResult"]
+           "densify_and_prune", "DensifyResult", "knn_mean_dist2"]
 __version__ = "0.1.0"

@@ -140,12 +140,17 @@ class hs_activate_args(C.Structure):
                 ("dL_dopacities", _fp), ("dL_dscales", _fp), ("dL_drotations", _fp)]
 
 
+class hs_knn_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("xyz", _fp), ("mean_d2", _fp), ("workspace", _fp), ("status", _fp)]
+
+
 EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
            "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
            "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
            "hs_adam_state_bytes", "hs_adam_step",
            "hs_densify_workspace_bytes", "hs_densify_plan", "hs_densify_apply",
-           "hs_activate", "hs_activate_backward", "hs_max_frames")
+           "hs_activate", "hs_activate_backward", "hs_max_frames",
+           "hs_knn_workspace_bytes", "hs_knn_mean_dist_sq")
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a
 # library without it reads hs_dims.n_frames as the reserved word it was and would render all poses into ONE image, silently
 # -- max_frames() is what a request for frames is checked against
@@ -219,6 +224,10 @@ def load() -> C.CDLL:
     lib.hs_activate.restype = C.c_int
     lib.hs_activate_backward.argtypes = [C.POINTER(hs_activate_args), C.c_void_p]
     lib.hs_activate_backward.restype = C.c_int
+    lib.hs_knn_workspace_bytes.argtypes = [C.c_int64]
+    lib.hs_knn_workspace_bytes.restype = C.c_int64
+    lib.hs_knn_mean_dist_sq.argtypes = [C.POINTER(hs_knn_args), C.c_void_p]
+    lib.hs_knn_mean_dist_sq.restype = C.c_int
     if hasattr(lib, "hs_max_frames"):
         lib.hs_max_frames.argtypes = []
         lib.hs_max_frames.restype = C.c_int

@@ -2235,13 +2235,13 @@ int64_t sort_tmp_bytes(int64_t n) {
 // separate arrays).  Ping-pongs between (k0,v0) and (k1,v1); the result lands in (k0,v0) when sort_passes(nbits) is
 // even, else in (k1,v1).  `fail_word`: device word that reads 2 afterwards if a look-back gave up.
 int launch_radix_sort(uint64_t* k0, uint32_t* v0, uint64_t* k1, uint32_t* v1, const uint32_t* n_dev,
-                      int64_t n_launch, int nbits, void* tmp, uint32_t* fail_word, hipStream_t s) {
+                      int64_t n_launch, int nbits, void* tmp, uint32_t* fail_word, hipStream_t s, bool zeroed) {
     if (n_launch <= 0) return HS_OK;
     constexpr int ITEMS = kU64SortItems, TILE = ITEMS * kSortBlock;
     const int nblk = ceil_div(n_launch, TILE);
     const int passes = sort_passes(nbits);
     const SortScratch sc(tmp, n_launch, TILE);
-    HS_HIP_CHECK(hipMemsetAsync(tmp, 0, (size_t)sort_scratch_words(n_launch, passes, TILE) * 4, s));
+    if (!zeroed) HS_HIP_CHECK(hipMemsetAsync(tmp, 0, (size_t)sort_scratch_words(n_launch, passes, TILE) * 4, s));
     if (fault_injection() == 1)   // tests only (HS_FAULT_INJECT=sort_ticket): chain position 0 is never handed out
         HS_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)sc.tickets, 1, 1, s));
     radix_ghist_kernel<uint64_t, false><<<ceil_div(n_launch, kHistTile), kHistThreads, 0, s>>>(k0, n_dev, nbits, passes, sc.ghist);

@@ -171,8 +171,10 @@ static inline int64_t pair_scratch_words(int64_t I, int64_t capacity, int passes
 // (u32 key, u32 value) elements with the same pass kernel).  Ping-pongs between (k0,v0) and (k1,v1); the result lands
 // in (k0,v0) when sort_passes(nbits) is even, else in (k1,v1).  `n_dev` points at the device-resident element count
 // (<= n_launch); `tmp` must hold sort_tmp_bytes(n_launch); *fail_word reads 2 afterwards if a look-back gave up.
+// `zeroed`: an earlier kernel on the stream cleared sort_scratch_words(n_launch, sort_passes(nbits), kU64Tile) words of `tmp`
+// (knn.hip, which enqueues kernels only); otherwise a memset node does.
 int launch_radix_sort(uint64_t* k0, uint32_t* v0, uint64_t* k1, uint32_t* v1, const uint32_t* n_dev,
-                      int64_t n_launch, int nbits, void* tmp, uint32_t* fail_word, hipStream_t s);
+                      int64_t n_launch, int nbits, void* tmp, uint32_t* fail_word, hipStream_t s, bool zeroed = false);
 // Test hook, compiled into libhdrsplat_test.so only (-DHS_TESTING; `make test_lib`): HS_FAULT_INJECT in the environment,
 // read once.  0 = none; 1 = "sort_ticket": hs_sort_pairs starts its first pass with ticket 1, so chain position 0 never
 // publishes and the bounded look-back must give up; 2 = "stalled_chain": the binning stage starts with the verdict of a

@@ -1,7 +1,7 @@
 """Scene I/O either side of the rasterizer: Gaussian clouds as PLY in the layout every 3DGS
 trainer and viewer exchanges, and COLMAP sparse reconstructions (the "SfM" arrow of
-/root/reference/assets/pipeline.png) as initialisation.  Host-side numpy code, no GPU work: the rasterizer takes the
-tensors these functions return.
+/root/reference/assets/pipeline.png) as initialisation.  Host-side numpy code, no GPU work -- except init_from_points(..., device="cuda"), whose
+neighbour search is the library's (knn.py) --: the rasterizer takes the tensors these functions return.
 
 PLY layout (binary little endian or ascii, one `vertex` element), properties in this order:
     x y z  nx ny nz  f_dc_0..2  f_rest_0..3*(M-1)-1  opacity  scale_0..2  rot_0..3
@@ -291,9 +291,36 @@ def colmap_view(image: ColmapImage, camera: ColmapCamera, znear: float = 0.01, z
     return V.float().contiguous(), full.float().contiguous(), campos, tanfovx, tanfovy
 
 
-def init_from_points(xyz: np.ndarray, rgb: np.ndarray, sh_degree: int = 3, initial_opacity: float = 0.1) -> GaussianCloud:
+def _init_from_points_gpu(xyz, rgb, sh_degree: int, initial_opacity: float, device) -> GaussianCloud:
+    """init_from_points on a CUDA device: the neighbour distances from knn.knn_mean_dist2 (fp32, HIP), everything else as
+    on the host path -- the floor, log sqrt and the colour in float64, rounded to float32 once."""
+    from .knn import knn_mean_dist2
+    device = torch.device(device)
+    pts = (xyz.detach() if isinstance(xyz, torch.Tensor) else torch.from_numpy(np.asarray(xyz)))
+    pts = pts.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
+    P = pts.shape[0]
+    M = (sh_degree + 1) ** 2
+    d2 = knn_mean_dist2(pts).double() if P > 1 else torch.ones(P, dtype=torch.float64, device=device)
+    log_s = torch.log(torch.sqrt(torch.clamp_min(d2, 1e-7)))
+    col = (rgb.detach().to(device) if isinstance(rgb, torch.Tensor) else torch.from_numpy(np.asarray(rgb)).to(device))
+    sh = torch.zeros(P, M, 3, dtype=torch.float32, device=device)
+    sh[:, 0, :] = ((col.double().reshape(-1, 3) / 255.0 - 0.5) / SH_C0).float()
+    rot = torch.zeros(P, 4, dtype=torch.float32, device=device)
+    rot[:, 0] = 1.0
+    logit = math.log(initial_opacity / (1.0 - initial_opacity))
+    return GaussianCloud(pts, sh, torch.full((P, 1), logit, dtype=torch.float32, device=device),
+                         log_s[:, None].repeat(1, 3).float().contiguous(), rot)
+
+
+def init_from_points(xyz, rgb, sh_degree: int = 3, initial_opacity: float = 0.1, device=None) -> GaussianCloud:
     """The published SfM initialisation: SH DC from the point colour, isotropic scale = distance scale of the three
-    nearest neighbours (sqrt of the mean squared distance, floored at 1e-7), identity rotation, opacity 0.1."""
+    nearest neighbours (sqrt of the mean squared distance, floored at 1e-7), identity rotation, opacity 0.1.
+    `device`: None (and host inputs) = on the host with scipy's k-d tree, CPU tensors; a CUDA device, or CUDA tensor
+    inputs, = the neighbour search in HIP (knn.knn_mean_dist2) and the cloud on that device, without scipy."""
+    if device is None:
+        device = next((t.device for t in (xyz, rgb) if isinstance(t, torch.Tensor) and t.device.type == "cuda"), None)
+    if device is not None and torch.device(device).type == "cuda":
+        return _init_from_points_gpu(xyz, rgb, sh_degree, initial_opacity, device)
     from scipy.spatial import cKDTree
     xyz = np.asarray(xyz, np.float64)
     P = xyz.shape[0]

@@ -622,6 +622,36 @@ typedef struct hs_activate_args {
 HS_API int hs_activate(const hs_activate_args* args, void* hip_stream);
 HS_API int hs_activate_backward(const hs_activate_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Mean squared distance to the three nearest neighbours of every point (knn.hip):
+ * the isotropic scale of the published SfM initialisation (upstream: simple_knn.distCUDA2).  For every point i of xyz [P, 3],
+ * over all j != i -- excluded BY INDEX, not by distance --
+ *     d2(i, j)   = ((dx dx) + (dy dy)) + (dz dz)                 dx = x_i - x_j ...
+ *     mean_d2[i] = ((b0 + b1) + b2) / (float)k                   b0 <= b1 <= b2 the k = min(3, P - 1) smallest d2(i, .)
+ * (fewer addends for k < 3; 0.0f for P = 1).  fp32, every operation one correctly rounded IEEE operation, nothing
+ * contracted, denormals kept; coincident points give exact zeros.  Only values are returned, never neighbour indices: the
+ * result is unique whatever order the candidates are visited in, and the same inputs give the same bits.  The search is
+ * exact: Morton order (30-bit codes, sorted by the radix passes of HS_STAGE_BIN), boxes of 64 consecutive points pruned by a
+ * lower bound that never exceeds a computed distance.  Cost grows to O(P^2 / 64) for clouds whose boxes prune nothing
+ * (DESIGN.md section 4.19).  Coordinates must be finite (the Python front end checks; here they only decide the values).
+ * Kernels only, on the caller's stream: no memset, no copy, no allocation, no synchronisation, no floating-point atomics.
+ * `status` (device) reads 0 afterwards, or 2 when a radix pass gave up waiting on its look-back chain: mean_d2 is then
+ * invalid (every access still stays inside the arrays).  Nothing at or beyond row P of mean_d2 and nothing beyond
+ * hs_knn_workspace_bytes(P) bytes of the workspace is written.
+ * Limits (HS_EINVAL, reported before any HIP call): 0 <= P < 2^30; no null pointer; xyz, mean_d2, status 4-byte aligned,
+ * workspace 256-byte aligned.  P == 0 is a successful no-op (nothing is launched, status is not written). */
+typedef struct hs_knn_args {
+    int64_t P;              /* points */
+    const float* xyz;       /* [P, 3] */
+    float* mean_d2;         /* [P] out */
+    void* workspace;        /* hs_knn_workspace_bytes(P) bytes, 256-byte aligned; carved inside */
+    uint32_t* status;       /* device word, out: 0 ok, 2 the sort gave up (results invalid) */
+} hs_knn_args;
+
+/* non-decreasing in P, a multiple of 256; -1 (HS_EINVAL) unless 0 <= P < 2^30.  ("dist_sq": the Python front end is
+ * knn_mean_dist2; exported names of this header carry no digits) */
+HS_API int64_t hs_knn_workspace_bytes(int64_t P);
+HS_API int hs_knn_mean_dist_sq(const hs_knn_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
