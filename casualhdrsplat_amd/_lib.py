@@ -144,13 +144,31 @@ class hs_knn_args(C.Structure):
     _fields_ = [("P", C.c_int64), ("xyz", _fp), ("mean_d2", _fp), ("workspace", _fp), ("status", _fp)]
 
 
+HS_MCMC_RELOCATE, HS_MCMC_GROW = 0, 1
+HS_MCMC_COUNTS = 8
+
+
+class hs_mcmc_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("n_draws", C.c_int64), ("mode", C.c_int32), ("flags", C.c_int32),
+                ("o_min", C.c_float), ("reserved", C.c_float), ("min_opacity", C.c_double),
+                ("opacities", _fp), ("scales", _fp), ("u", _fp), ("workspace", _fp), ("row_map", _fp), ("counts", _fp),
+                ("counts_host", _fp), ("matrices", C.POINTER(hs_densify_matrix)), ("n_matrices", C.c_int32),
+                ("reserved2", C.c_int32)]
+
+
+class hs_mcmc_noise_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("flags", C.c_int32), ("scaler", C.c_float),
+                ("means3D", _fp), ("opacities", _fp), ("scales", _fp), ("rotations", _fp), ("xi", _fp)]
+
+
 EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
            "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
            "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
            "hs_adam_state_bytes", "hs_adam_step",
            "hs_densify_workspace_bytes", "hs_densify_plan", "hs_densify_apply",
            "hs_activate", "hs_activate_backward", "hs_max_frames",
-           "hs_knn_workspace_bytes", "hs_knn_mean_dist_sq")
+           "hs_knn_workspace_bytes", "hs_knn_mean_dist_sq",
+           "hs_mcmc_workspace_bytes", "hs_mcmc_sample", "hs_mcmc_update", "hs_mcmc_noise")
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a
 # library without it reads hs_dims.n_frames as the reserved word it was and would render all poses into ONE image, silently
 # -- max_frames() is what a request for frames is checked against
@@ -228,6 +246,14 @@ def load() -> C.CDLL:
     lib.hs_knn_workspace_bytes.restype = C.c_int64
     lib.hs_knn_mean_dist_sq.argtypes = [C.POINTER(hs_knn_args), C.c_void_p]
     lib.hs_knn_mean_dist_sq.restype = C.c_int
+    lib.hs_mcmc_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
+    lib.hs_mcmc_workspace_bytes.restype = C.c_int64
+    lib.hs_mcmc_sample.argtypes = [C.POINTER(hs_mcmc_args), C.c_void_p]
+    lib.hs_mcmc_sample.restype = C.c_int
+    lib.hs_mcmc_update.argtypes = [C.POINTER(hs_mcmc_args), C.c_void_p]
+    lib.hs_mcmc_update.restype = C.c_int
+    lib.hs_mcmc_noise.argtypes = [C.POINTER(hs_mcmc_noise_args), C.c_void_p]
+    lib.hs_mcmc_noise.restype = C.c_int
     if hasattr(lib, "hs_max_frames"):
         lib.hs_max_frames.argtypes = []
         lib.hs_max_frames.restype = C.c_int

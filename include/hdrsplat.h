@@ -582,6 +582,106 @@ HS_API int64_t hs_densify_workspace_bytes(int64_t P);
 HS_API int hs_densify_plan(const hs_densify_args* args, void* hip_stream);
 HS_API int hs_densify_apply(const hs_densify_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) MCMC refinement of the cloud (mcmc.hip): the relocation, the growth and the
+ * position noise of "3D Gaussian Splatting as Markov Chain Monte Carlo".  A fixed row budget, a size the host knows before
+ * any kernel runs, and dead rows moved onto live ones in place: nothing here is read back, nothing synchronises, allocates,
+ * sets or copies memory; the caller owns every byte.  The library holds no random-number generator: every random input is a
+ * caller-drawn tensor, and the same inputs give the same bits.
+ *
+ * SAMPLING BY OPACITY (hs_mcmc_sample), per row i of P:
+ *     dead_i = !(opacities[i] > o_min)         compared AS STORED (o_min is a logit with HS_DENSIFY_RAW_OPACITY: the host
+ *                                              converts min_opacity once, in fp64, and rounds to fp32); a NaN is dead
+ *     w_i    = (uint64) rint(2^24 / (1 + exp(-(double)opacities[i])))     exp in fp64, rint to nearest-even
+ *              without HS_DENSIFY_RAW_OPACITY: rint(2^24 * min(max((double)opacities[i], 0), 1))
+ *              0 for a NaN; HS_MCMC_RELOCATE: 0 for a dead row; HS_MCMC_GROW: every other row keeps its weight
+ *     C_i    = w_0 + ... + w_i   (uint64, exact whatever the order; S = C_{P-1} < 2^54)
+ * A draw takes a 64-bit word u (the int64 tensor `u` read as uint64): t = floor(u S / 2^64) (the high word of the 128-bit
+ * product), and its source is the first i with C_i > t: a row of weight zero is never chosen.  With S == 0 no draw is made,
+ * cnt stays zero and hs_mcmc_update changes nothing.
+ *   HS_MCMC_RELOCATE  n_draws == P: every DEAD row i draws with u[i] (its own row: no compaction); sources[i] = its source, -1
+ *                     for rows that are not dead (and for every row when S == 0)
+ *   HS_MCMC_GROW      draw k of n_draws <= P uses u[k]; sources[k] = its source (-1 when S == 0), and
+ *                     row_map[j] = j for j < P, row_map[P + k] = HS_DENSIFY_KIND_CLONE << 30 | sources[k]: hs_densify_apply's
+ *                     format, survivors then clones in draw order (when S == 0 the clones name row k mod P, so that the
+ *                     gather stays inside the cloud)
+ * cnt[src] = the number of draws that chose src (u32, integer atomic adds: order-free).
+ * counts[HS_MCMC_COUNTS] (u32) = {P, dead rows, draws made, sources (rows with cnt >= 1), S == 0, 0, 0, 0}, and a copy at
+ * counts_host (NULL, or a page-locked host address as hs_densify_args.counts_host is; written by the call's last kernel).
+ * Three kernels (four with counts_host): weights with their prefix inside each block of 256 rows and the block sums, ONE
+ * small scan of the block sums, the draws (two binary searches: blocks, then rows of the block).
+ * Workspace: hs_mcmc_workspace_bytes(P, n_draws) = align256(8 P) + align256(16 (ceil(P / 256) + 1)) + align256(4 P) +
+ * align256(4 n_draws) bytes, 16-byte aligned, in that order: u64 inner prefixes [P] (row i: w of its block up to and
+ * including i) | per block {u64 exclusive prefix, u32 dead rows, u32 0}, then {S, dead rows, 0} | u32 cnt [P] | i32 sources
+ * [n_draws].  hs_mcmc_update reads cnt and sources there: both calls take the same struct.
+ *
+ * UPDATE (hs_mcmc_update), in place, two kernels.  Every row with c = cnt[i] >= 1, in fp64, each result rounded once to fp32:
+ *     r = min(c + 1, 51);  o = 1 / (1 + exp(-opacities[i]))  (the stored value without HS_DENSIFY_RAW_OPACITY)
+ *     x = 1 - pow(1 - o, 1 / r)
+ *     D = sum_{n = 1..r} sum_{k = 0..n-1} C(n-1, k) (-1)^k x^(k+1) / sqrt(k + 1)     in this loop order, x^(k+1) a running
+ *                                                                                   product, the binomials exact
+ *     x_c = min(max(x, min_opacity), 1 - 2^-23)
+ *     opacities[i] <- log(x_c / (1 - x_c))     (x_c without HS_DENSIFY_RAW_OPACITY)
+ *     scales[3i+j] <- scales[3i+j] + log(o / D)     (scales[3i+j] * (o / D) without HS_DENSIFY_RAW_SCALES)
+ * Then, HS_MCMC_RELOCATE only, over the matrices {dst [P, row_stride], role; src NULL or dst}: in HS_DENSIFY_COPY matrices
+ * (the parameters) every dead row i becomes a bit-exact copy of row sources[i] as the first kernel left it; in
+ * HS_DENSIFY_ZERO_NEW matrices (Adam's moments) every row with cnt >= 1 becomes zeros.  The moments of dead rows, and every
+ * row that is neither dead nor a source, keep their bits.  HS_MCMC_GROW runs the first kernel only (the moments of a grown
+ * source are kept); the new rows are hs_densify_apply's gather over row_map (roles COPY / ZERO_NEW, P_out = P + n_draws).
+ *
+ * POSITION NOISE (hs_mcmc_noise), one kernel, one row per thread, fp32, every operation one correctly rounded IEEE operation
+ * plus the library expf, nothing contracted, no atomics:
+ *     o   = 1 / (1 + expf(-opacities[i]))      (the stored value without HS_DENSIFY_RAW_OPACITY)
+ *     g   = 1 / (1 + expf(-100 * ((1 - o) - 0.995f)));   gs = g * scaler;   gs == 0: the row is not written
+ *     (w, x, y, z) = rotations[4i..] / sqrtf(((w w + x x) + y y) + z z),  R as in hs_densify_apply's MEANS role
+ *     s_j = expf(scales[3i+j])   (the stored value without HS_DENSIFY_RAW_SCALES);   v_j = xi[3i+j] * gs
+ *     b_j = (s_j s_j) * ((R0j v_0 + R1j v_1) + R2j v_2)
+ *     means3D[3i+c] <- ((Rc0 b_0 + Rc1 b_1) + Rc2 b_2) + means3D[3i+c]
+ * i.e. mu + R diag(s^2) R^T (xi g scaler), with `xi` [P, 3] standard normals and scaler = lr_xyz * noise_lr a host scalar.
+ * Pointers need 4-byte alignment only (the quaternion is one 16-byte load where its address allows), u 8 bytes.
+ * Limits (HS_EINVAL, reported before any HIP call): 0 <= P < 2^30; mode one of HS_MCMC_*; flags within HS_DENSIFY_RAW_*;
+ * n_draws == P (RELOCATE) or 0 <= n_draws <= P (GROW); o_min not NaN; 0 <= min_opacity <= 1; 0 <= n_matrices <= 16, roles
+ * COPY / ZERO_NEW, row_stride >= 1, P * row_stride < 2^40; scaler finite.  With P == 0 no data pointer is looked at (the
+ * sample still writes its counts: {0, 0, 0, 0, 1, 0, 0, 0} -- an empty cloud has S == 0). */
+#define HS_MCMC_RELOCATE 0
+#define HS_MCMC_GROW 1
+#define HS_MCMC_COUNTS 8
+typedef struct hs_mcmc_args {
+    int64_t P;                    /* rows */
+    int64_t n_draws;              /* RELOCATE: P (one slot per row); GROW: the new rows */
+    int32_t mode;                 /* HS_MCMC_RELOCATE / HS_MCMC_GROW */
+    int32_t flags;                /* HS_DENSIFY_RAW_* */
+    float o_min;                  /* stored space: rows not above it are dead: sample */
+    float reserved;
+    double min_opacity;           /* activated space: lower clamp of a source's new opacity: update */
+    float* opacities;             /* [P]     read by the sample, updated in place by the update */
+    float* scales;                /* [P, 3]  updated in place by the update */
+    const int64_t* u;             /* [n_draws] random 64-bit words, read as uint64: sample */
+    void* workspace;              /* hs_mcmc_workspace_bytes(P, n_draws) bytes, 16-byte aligned: both */
+    uint32_t* row_map;            /* GROW: [P + n_draws], written by the sample (NULL for RELOCATE) */
+    uint32_t* counts;             /* device, [HS_MCMC_COUNTS]: written by the sample */
+    uint32_t* counts_host;        /* NULL, or a page-locked host address the GPU can write: the sample's copy of counts */
+    const hs_densify_matrix* matrices; /* HOST array of n_matrices descriptors (copied into the kernel's arguments): update */
+    int32_t n_matrices;
+    int32_t reserved2;
+} hs_mcmc_args;
+
+typedef struct hs_mcmc_noise_args {
+    int64_t P;
+    int32_t flags;                /* HS_DENSIFY_RAW_* */
+    float scaler;                 /* lr_xyz * noise_lr */
+    float* means3D;               /* [P, 3]  in place */
+    const float* opacities;       /* [P] */
+    const float* scales;          /* [P, 3] */
+    const float* rotations;       /* [P, 4] (w, x, y, z), not normalised */
+    const float* xi;              /* [P, 3] standard normals */
+} hs_mcmc_noise_args;
+
+/* the formula above; -1 (HS_EINVAL) unless 0 <= P < 2^30 and 0 <= n_draws < 2^30 */
+HS_API int64_t hs_mcmc_workspace_bytes(int64_t P, int64_t n_draws);
+HS_API int hs_mcmc_sample(const hs_mcmc_args* args, void* hip_stream);
+HS_API int hs_mcmc_update(const hs_mcmc_args* args, void* hip_stream);
+HS_API int hs_mcmc_noise(const hs_mcmc_noise_args* args, void* hip_stream);
+
 /* (detected by name; HS_VERSION unchanged) Activations of the STORED cloud (activate.hip).  A trainer stores logit opacities,
  * log scales and unnormalised quaternions -- what hs_adam_step updates and hs_densify_* compact -- while hs_forward /
  * hs_backward take opacities, scales and unit quaternions.  hs_activate computes the second from the first; hs_activate_backward
