@@ -272,6 +272,16 @@ int hs_plan(const hs_dims* dims, hs_sizes* sizes, hs_layout* layout) {
 
 int hs_max_frames(void) { return kMaxPoses; }   // (the limit on n_poses: every pose may be a frame of its own)
 
+#ifdef HS_TESTING
+// libhdrsplat_test.so only (not in hdrsplat.h, not in the product library): the stamp the NEXT single-enqueue hs_forward
+// of this process will carry (next_frame_tag), so that a test can plant words that already bear it in the binning
+// workspace -- hs_common.h, kDepthBitsAt: "garbage bits under a matching tag ... never a wrong order".  Reads, counts nothing.
+HS_API uint32_t hs_test_next_frame_tag(void) {
+    const uint32_t t = g_frame_tag.load(std::memory_order_relaxed) + 1u;
+    return t == 0u ? 1u : t;
+}
+#endif
+
 int hs_forward(const hs_fwd_args* a, void* hip_stream) {
     if (!a) { set_error("hs_forward: null args"); return HS_EINVAL; }
     hipStream_t s = (hipStream_t)hip_stream;

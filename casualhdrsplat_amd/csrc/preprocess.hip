@@ -950,7 +950,10 @@ __global__ void __launch_bounds__(256) pose_reduce1_kernel(const float* partials
     const int per = (nblk + kPoseChunks - 1) / kPoseChunks;
     const int r0 = chunk * per, r1 = min(nblk, r0 + per);
     float acc = 0.f;
-    for (int r = r0; r < r1; ++r) acc += partials[(int64_t)r * cols + col];
+    // (value kPoseVals - 1 of a row is padding: preprocess_bwd_kernel writes the 27 pose terms, nobody the 28th -- it is not
+    // read here either, the workspace holds whatever the caller's allocator left there)
+    if (col % kPoseVals != kPoseVals - 1)
+        for (int r = r0; r < r1; ++r) acc += partials[(int64_t)r * cols + col];
     stage[(int64_t)chunk * cols + col] = acc;
 }
 // One thread per OUTPUT element -- 16 + 16 + 3 per pose -- so that the matrix entries no pose term maps to (column 3 of the view

@@ -672,14 +672,16 @@ __global__ void __launch_bounds__(256) resolve_kernel(int64_t HW, int N, int F, 
 // in strip order EXCEPT its lightest ones, which go to the queue the last workgroups serve (render_bwd_kernel) -- the
 // launch then ends on short tiles, and its tail is as long as one of those instead of an average one.  Weight of a
 // tile = the trips the forward counted on it; "lightest" by a histogram of the weights (two trips per bin; ties inside
-// the threshold bin are broken by arrival, any choice is as good).  The order is a permutation of the tiles whatever
-// the weights are, and results do not depend on it.
+// the threshold bin go to the first tiles of the strip order, and the queue lists its tiles in strip order too: the order
+// is a function of the weights alone -- it used to depend on which lane's atomic arrived first, so two runs of one frame
+// left different bytes in hs_layout.tile_order).  The order is a permutation of the tiles whatever the weights are, and
+// results do not depend on it.
 __global__ void __launch_bounds__(1024) order_tiles_kernel(int nb, int gx, int n_static, const uint32_t* work,
                                                            uint32_t* order) {
     constexpr int kBins = 1024, kT = 1024;
     __shared__ uint32_t s_hist[kBins];
     __shared__ uint32_t s_scan[kT / 64];
-    __shared__ uint32_t s_thr_bin, s_thr_take, s_cnt_thr, s_cnt_q;
+    __shared__ uint32_t s_thr_bin, s_thr_take;
     const int x = blockIdx.x, t = threadIdx.x;
     const int per = nb / 8, rem = nb % 8;
     const int cnt = per + (x < rem ? 1 : 0);                               // tiles (= blocks) of XCD x
@@ -707,7 +709,7 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(int nb, int gx, int n
     };
     auto bin_of = [&](int k) { return (int)min((uint32_t)(kBins - 1), work[xcd_strip_tile(x + 8 * k, nb, gx)] >> 1); };
     s_hist[t] = 0;
-    if (t == 0) { s_thr_bin = 0; s_thr_take = 0; s_cnt_thr = 0; s_cnt_q = 0; }
+    if (t == 0) { s_thr_bin = 0; s_thr_take = 0; }
     __syncthreads();
     for (int k = k0; k < k1; ++k) atomicAdd(&s_hist[bin_of(k)], 1u);
     __syncthreads();
@@ -720,19 +722,27 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(int nb, int gx, int n
     __syncthreads();
     const int thr = (int)s_thr_bin;
     const uint32_t take = s_thr_take;
+    // tiles of the threshold bin in front of this thread's, in strip order: the first `take` of the bin are light
+    uint32_t in_thr = 0;
+    for (int k = k0; k < k1; ++k) in_thr += bin_of(k) == thr ? 1u : 0u;
+    uint32_t tot_thr;
+    uint32_t thr_rank = block_excl_scan(in_thr, &tot_thr);
     uint64_t light_mask = 0;
     uint32_t kept = 0;
     for (int k = k0; k < k1; ++k) {
         const int b = bin_of(k);
-        const bool light = n_light > 0 && (b < thr || (b == thr && atomicAdd(&s_cnt_thr, 1u) < take));
+        const bool light = n_light > 0 && (b < thr || (b == thr && thr_rank++ < take));
         light_mask |= (uint64_t)light << (k - k0);
         kept += !light;
     }
     uint32_t tot_kept;
     uint32_t kpos = block_excl_scan(kept, &tot_kept);   // kept tiles stay in strip order
+    // ... and so do the light ones in the queue: every thread in front of one that has tiles has exactly E of them, so
+    // k0 tiles lie in front of this thread's, kpos of them kept
+    uint32_t qpos = (uint32_t)k0 - kpos;
     for (int k = k0; k < k1; ++k) {
         const uint32_t vt = (uint32_t)xcd_strip_tile(x + 8 * k, nb, gx);
-        if ((light_mask >> (k - k0)) & 1ull) order[n_static + q_base + (int)atomicAdd(&s_cnt_q, 1u)] = vt;
+        if ((light_mask >> (k - k0)) & 1ull) order[n_static + q_base + (int)qpos++] = vt;
         else order[x + 8 * (int)kpos++] = vt;
     }
 }

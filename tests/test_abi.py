@@ -52,6 +52,16 @@ def test_fault_injection_exists_only_in_the_test_library(lib):
     out = subprocess.check_output(["nm", "-D", "--defined-only", test_path]).decode()
     for n in header_functions():
         assert re.search(rf"\bT {n}\b", out), n
+    # ... plus ONE export of its own, which no header declares and the product library does not have: the frame tag the next
+    # hs_forward will draw (tests/test_workspace_contents_gpu.py plants words that already carry it)
+    extra = [ln.split()[-1] for ln in out.splitlines() if ln.strip()]
+    extra = [n for n in extra if n not in header_functions() and not n.startswith("__hip_cuid_")]
+    assert extra == ["hs_test_next_frame_tag"], extra
+    assert b"hs_test_next_frame_tag" not in prod
+    dll = C.CDLL(test_path)
+    dll.hs_test_next_frame_tag.restype = C.c_uint32
+    t = dll.hs_test_next_frame_tag()
+    assert t != 0 and t == dll.hs_test_next_frame_tag()      # asking draws nothing
 
 
 def test_the_library_reads_no_sort_switch_from_the_environment(lib):
