@@ -6,7 +6,7 @@ that consumes its images (losses.photometric_loss, losses.ssim) and the fused, v
 Adam step that applies the gradients (optim.GaussianAdam), and the densify / prune of the cloud that
 changes the number of Gaussians under that optimizer (densify.densify_and_prune), and the neighbour
 distances that size a new cloud (knn.knn_mean_dist2, scene_io.init_from_points), and the MCMC policy's
-relocation, growth and position noise (mcmc.relocate, mcmc.grow, mcmc.inject_noise).  Compute lives in
+relocation, growth, position noise and regularisers (mcmc.relocate, mcmc.grow, mcmc.inject_noise, mcmc.regularize).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
@@ -14,7 +14,7 @@ missing library is a hard error (no CPU fallback).
 from .densify import DensifyResult, densify_and_prune
 from .knn import knn_mean_dist2
 from .losses import photometric_loss, ssim
-from .mcmc import GrowResult, RelocateResult, grow, inject_noise, relocate
+from .mcmc import GrowResult, RelocateResult, grow, inject_noise, regularize, relocate
 from .optim import GaussianAdam, cloud_param_groups
 from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSettings, GaussianRasterizer,
                          SortChainStalled, inspect_state, rasterize_gaussians)
@@ -22,5 +22,5 @@ from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSet
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats", "BinningOverflow", "SortChainStalled",
            "rasterize_gaussians", "inspect_state", "photometric_loss", "ssim", "GaussianAdam", "cloud_param_groups",
            "densify_and_prune", "DensifyResult", "knn_mean_dist2",
-           "relocate", "grow", "inject_noise", "RelocateResult", "GrowResult"]
+           "relocate", "grow", "inject_noise", "regularize", "RelocateResult", "GrowResult"]
 __version__ = "0.1.0"

@@ -161,6 +161,13 @@ class hs_mcmc_noise_args(C.Structure):
                 ("means3D", _fp), ("opacities", _fp), ("scales", _fp), ("rotations", _fp), ("xi", _fp)]
 
 
+class hs_mcmc_reg_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("flags", C.c_int32), ("reserved", C.c_int32),
+                ("lambda_opacity", C.c_double), ("lambda_scale", C.c_double),
+                ("opacities", _fp), ("scales", _fp), ("dL_dopacities", _fp), ("dL_dscales", _fp),
+                ("loss", _fp), ("workspace", _fp)]
+
+
 EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
            "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
            "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
@@ -168,7 +175,8 @@ EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward"
            "hs_densify_workspace_bytes", "hs_densify_plan", "hs_densify_apply",
            "hs_activate", "hs_activate_backward", "hs_max_frames",
            "hs_knn_workspace_bytes", "hs_knn_mean_dist_sq",
-           "hs_mcmc_workspace_bytes", "hs_mcmc_sample", "hs_mcmc_update", "hs_mcmc_noise")
+           "hs_mcmc_workspace_bytes", "hs_mcmc_sample", "hs_mcmc_update", "hs_mcmc_noise",
+           "hs_mcmc_reg_workspace_bytes", "hs_mcmc_regularize")
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a
 # library without it reads hs_dims.n_frames as the reserved word it was and would render all poses into ONE image, silently
 # -- max_frames() is what a request for frames is checked against
@@ -254,6 +262,10 @@ def load() -> C.CDLL:
     lib.hs_mcmc_update.restype = C.c_int
     lib.hs_mcmc_noise.argtypes = [C.POINTER(hs_mcmc_noise_args), C.c_void_p]
     lib.hs_mcmc_noise.restype = C.c_int
+    lib.hs_mcmc_reg_workspace_bytes.argtypes = [C.c_int64]
+    lib.hs_mcmc_reg_workspace_bytes.restype = C.c_int64
+    lib.hs_mcmc_regularize.argtypes = [C.POINTER(hs_mcmc_reg_args), C.c_void_p]
+    lib.hs_mcmc_regularize.restype = C.c_int
     if hasattr(lib, "hs_max_frames"):
         lib.hs_max_frames.argtypes = []
         lib.hs_max_frames.restype = C.c_int

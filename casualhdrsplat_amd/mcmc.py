@@ -1,10 +1,13 @@
-"""MCMC refinement of the cloud (mcmc.hip, through hs_mcmc_sample / hs_mcmc_update / hs_mcmc_noise of include/hdrsplat.h):
-the second published densification policy, "3D Gaussian Splatting as Markov Chain Monte Carlo" -- a fixed row budget, dead
-Gaussians moved onto live ones instead of pruned, and a position noise after every optimizer step.
+"""MCMC refinement of the cloud (mcmc.hip and mcmc_reg.hip, through hs_mcmc_sample / hs_mcmc_update / hs_mcmc_noise /
+hs_mcmc_regularize of include/hdrsplat.h): the second published densification policy, "3D Gaussian Splatting as Markov Chain
+Monte Carlo" -- a fixed row budget, dead Gaussians moved onto live ones instead of pruned, a position noise after every
+optimizer step, and the opacity / scale regularisers that make Gaussians die.
 
     opt = GaussianAdam(cloud_param_groups(means3D, raw_opacities, shs, log_scales, rotations), eps=1e-15)
     ...
-    opt.step(visibility=radii)
+    loss.backward()
+    terms = regularize(opt, opacity_reg=0.01, scale_reg=0.01)   # += d(lambda_o mean|o| + lambda_s mean|s|) into .grad, in place
+    opt.step()                                           # every row: the regularisers act on Gaussians no frame saw, too
     inject_noise(opt, noise_lr=5e5)                      # every step, one launch
     if step % 100 == 0:
         relocate(opt, min_opacity=0.005)                 # in place: P does not change, nothing is read back
@@ -21,7 +24,12 @@ No host wait anywhere: `relocate` and `inject_noise` change the optimizer's tens
 computed on the host, gathers with hs_densify_apply (new rows get zero moments) and hands the tensors to
 GaussianAdam.replace_params, so the device step count and running products are not touched.  Counts stay on the device.
 
-Not here: WHEN to refine, and the opacity / scale regularisers of the publication (two torch lines on the stored leaves).
+The regularisers are a call, not two torch lines: under parameterization="raw" the rasterizer's backward hands the stored
+opacities and scales a .grad that is a view into its one flat gradient buffer, and a second autograd contribution to the
+same leaf would make the engine sum the two into a tensor of its own -- the view, which the chunked all-reduce and
+GaussianAdam rely on, would be lost.  `regularize` adds into the rows that exist (one launch, two with the values).
+
+Not here: WHEN to refine (examples/train_synthetic.py --mcmc shows one schedule).
 
 GPU tensors only, fp32 only: anything else raises (no fallback).
 """
@@ -238,3 +246,59 @@ def inject_noise(optimizer, *, noise_lr=5e5, lr=None, raw_scales=True, raw_opaci
     a.rotations, a.xi = cloud["rotations"].data_ptr(), xi.data_ptr()
     with _on_device(dev):
         L.check(L.load().hs_mcmc_noise(C.byref(a), _stream(dev)), "hs_mcmc_noise")
+
+
+def _reg_weight(what, name, v):
+    v = float(v)
+    if not math.isfinite(v) or v < 0.0:
+        raise ValueError(f"{what}: {name}={v} must be finite and not negative")
+    return v
+
+
+def regularize(optimizer, *, opacity_reg=0.01, scale_reg=0.01, raw_scales=True, raw_opacity=True, value=True):
+    """The publication's regularisers opacity_reg * mean|opacity| + scale_reg * mean|scale| (activated values), as the
+    gradient they add: call after backward() and before optimizer.step().  Adds, in place, into the .grad of the cloud's
+    `opacity` and `scaling` tensors -- the tensors stay where they are (grad.data_ptr() does not change), so a .grad that is a
+    view of the rasterizer's flat gradient buffer remains one.  Returns the two terms as a float32 [2] tensor on the device
+    (reading it is the caller's wait), or None with value=False (one launch less).  A tensor whose weight is 0 is not touched
+    and needs no .grad.  The regularisers act on ALL rows, also those no frame of the step saw: an MCMC step is
+    `optimizer.step()` without visibility= (a masked step would leave the unseen rows' gradient unapplied)."""
+    what = "regularize"
+    cloud = _cloud_of(optimizer)
+    lam_o, lam_s = _reg_weight(what, "opacity_reg", opacity_reg), _reg_weight(what, "scale_reg", scale_reg)
+    P, dev = int(cloud["means3D"].shape[0]), cloud["means3D"].device
+    grads = {}
+    for key, lam in (("opacities", lam_o), ("scales", lam_s)):
+        if lam == 0.0:
+            grads[key] = None
+            continue
+        p = cloud[key]
+        g = p.grad
+        if g is None:
+            raise ValueError(f"{what}: the {key} tensor has no .grad: call after backward()")
+        _require_gpu(g, f"the gradient of the {key}")
+        if g.dtype != torch.float32 or g.shape != p.shape or g.device != dev or not g.is_contiguous():
+            raise ValueError(f"{what}: the .grad of the {key} must be a contiguous float32 tensor of its parameter's shape and device")
+        grads[key] = g
+    if P >= 1 << 30:
+        raise ValueError(f"{what}: {P} Gaussians; the library's limit is 2^30 - 1")
+    if lam_o == 0.0 and lam_s == 0.0 and not value:
+        return None
+    lib = L.load()
+    a = L.hs_mcmc_reg_args()
+    a.P, a.lambda_opacity, a.lambda_scale = P, lam_o, lam_s
+    a.flags = (L.HS_DENSIFY_RAW_SCALES if raw_scales else 0) | (L.HS_DENSIFY_RAW_OPACITY if raw_opacity else 0)
+    a.opacities, a.scales = cloud["opacities"].data_ptr(), cloud["scales"].data_ptr()
+    a.dL_dopacities = None if grads["opacities"] is None else grads["opacities"].data_ptr()
+    a.dL_dscales = None if grads["scales"] is None else grads["scales"].data_ptr()
+    terms = workspace = None
+    if value:
+        nbytes = lib.hs_mcmc_reg_workspace_bytes(P)
+        if nbytes < 0:
+            L.check(L.HS_EINVAL, "hs_mcmc_reg_workspace_bytes")
+        workspace = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+        terms = torch.empty(2, dtype=torch.float32, device=dev)
+        a.loss, a.workspace = terms.data_ptr(), workspace.data_ptr()
+    with _on_device(dev):
+        L.check(lib.hs_mcmc_regularize(C.byref(a), _stream(dev)), "hs_mcmc_regularize")
+    return terms

@@ -13,6 +13,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --fused-adam           # the update through optim.GaussianAdam, visible rows only
     python examples/train_synthetic.py --steps 300 --fused-adam --raw     # the stored (logit) opacities go straight into the rasterizer
     python examples/train_synthetic.py --steps 300 --batch-frames         # all frames of a step in ONE rasterizer call
+    python examples/train_synthetic.py --steps 300 --mcmc                 # learn the WHOLE cloud from a quarter of the points: MCMC policy
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -29,7 +30,10 @@ sys.path.insert(0, ROOT)
 
 import torch
 
+from casualhdrsplat_amd import scene_io
 from casualhdrsplat_amd import synthetic as S
+from casualhdrsplat_amd.mcmc import grow, inject_noise, regularize, relocate
+from casualhdrsplat_amd.optim import cloud_param_groups
 from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.optim import GaussianAdam
 from casualhdrsplat_amd.graphs import GraphedStep
@@ -58,7 +62,8 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
-        graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False):
+        graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
+        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -70,7 +75,21 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     buffer -- and the fixed scales / rotations as logs / quaternions.
     batch_frames: the step is ONE rasterizer call over all frames (HDRBlurFormation.forward_frames, settings.n_frames) and
     one loss call over the [frames, 3, H, W] batch instead of a call per frame: the same gradients up to fp32 summation
-    order.  Eager only: together with graph=True it raises (the captured step keeps one rasterizer per frame)."""
+    order.  Eager only: together with graph=True it raises (the captured step keeps one rasterizer per frame).
+    mcmc: the learner does not know the cloud.  It starts from P // 4 of the true positions, noised, as
+    scene_io.init_from_points builds a cloud from points (3-NN scales, identity quaternions, opacity 0.1, DC from noised
+    true colours), and learns ALL FIVE stored tensors -- leaves of one GaussianAdam(cloud_param_groups(...)) that also holds
+    the exposure and trajectory groups -- under the MCMC policy: every step is gradients, regularize (the publication's
+    opacity_reg mean|opacity| + scale_reg mean|scale|, added in place into the rasterizer's gradient rows), opt.step() on
+    every row, inject_noise; every `refine_every` steps, from the first such step to steps - refine_every, relocate (dead
+    rows onto live ones) and grow towards `cap_max` (default P) by the factor, at most 2, that reaches the budget at the
+    last refinement.  Implies fused_adam and raw; eager only (P changes: not with graph=True).  The history gains P and the
+    two regulariser terms, and the reported loss is the mean per-frame loss plus the two terms."""
+    if mcmc and graph:
+        raise ValueError("mcmc=True (--mcmc) is not supported together with graph=True (--graph): the number of Gaussians "
+                         "changes at every refinement, a captured step is recorded for one size")
+    if mcmc:
+        fused_adam = raw = True
     if batch_frames and graph:
         raise ValueError("batch_frames=True (--batch-frames) is not supported together with graph=True (--graph): the captured "
                          "step is built around one persistent rasterizer per frame (image_formation.FrameRasterizers)")
@@ -113,9 +132,26 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     fixed = {k: cloud_true[k] for k in ("means3D", "scales", "rotations")}
     if raw:                                                  # (the stored form of the fixed tensors: the quaternions as they are)
         fixed["scales"] = fixed["scales"].log()
+    # what the rasterizer is given: the learnt radiance and opacities over the true geometry -- or, mcmc, five learnt tensors
+    cur = {"means3D": fixed["means3D"], "opacities": raw_opac, "shs": shs, "scales": fixed["scales"], "rotations": fixed["rotations"]}
     with torch.no_grad():
         model.log_exposure[0] = truth.log_exposure[0]       # the gauge (see the module docstring)
-    if fused_adam:
+    if mcmc:
+        P0 = max(P // 4, 4)
+        pick = torch.randperm(P, generator=gen)[:P0]
+        xyz0 = sc.means3D[pick] + 0.02 * torch.randn(P0, 3, generator=gen)
+        rgb0 = 255.0 * (scene_io.SH_C0 * (sc.shs[pick, 0] + 0.25 * torch.randn(P0, 3, generator=gen)) + 0.5)
+        start = scene_io.init_from_points(xyz0.to(dev), rgb0.to(dev), sh_degree=deg, initial_opacity=0.1, device=dev)
+        cur = {k: v.clone().requires_grad_(True) for k, v in start.stored(dev).items()}
+        groups = cloud_param_groups(*[cur[k] for k in CLOUD], lr=dict(means3D=2e-4, opacities=5e-2, shs_dc=1e-2, shs_rest=5e-4,
+                                                                       scales=5e-3, rotations=1e-3))
+        for g_ in groups:
+            g_["eps"] = 1e-15
+        opt = GaussianAdam(groups + [{"params": [model.log_exposure], "lr": 1e-2}, {"params": [model.trajectory.delta], "lr": 5e-4}])
+        cap = int(cap_max) if cap_max else P
+        refine_at = [it for it in range(refine_every, steps - refine_every + 1, refine_every)] if refine_every > 0 else []
+        gen_dev = torch.Generator(device=dev).manual_seed(seed + 3)
+    elif fused_adam:
         opt = GaussianAdam([
             {"params": [shs], "lr": 1e-2, "per_gaussian": True}, {"params": [raw_opac], "lr": 2e-2, "per_gaussian": True},
             {"params": [model.log_exposure], "lr": 1e-2}, {"params": [model.trajectory.delta], "lr": 5e-4}])
@@ -132,6 +168,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             return e_dt, e_pose
 
     learn = [shs, raw_opac, model.log_exposure, model.trajectory.delta]
+    if mcmc:
+        learn = [cur[k] for k in CLOUD] + [model.log_exposure, model.trajectory.delta]
 
     def gradients():
         """Forward of every frame + backward of the summed loss; returns (per-frame losses, per-frame MSE) as tensors."""
@@ -140,11 +178,11 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         # one pass over the spline for all frames (its few hundred tiny tensor operations are the step's host cost), one
         # rasterizer call per frame, one backward of the summed loss
         cams = model.cameras_all()
-        opac = raw_opac if raw else torch.sigmoid(raw_opac)
+        opac = cur["opacities"] if raw else torch.sigmoid(raw_opac)
         losses, mses = [], []
         for i in range(frames):
-            ldr, _, radii, _ = model(i, fixed["means3D"], opac, shs, fixed["scales"], fixed["rotations"], cameras=cams)
-            if fused_adam:            # (kernels only, written in place: the captured step leaves no copy node behind)
+            ldr, _, radii, _ = model(i, cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"], cameras=cams)
+            if fused_adam and not mcmc:   # (kernels only, written in place: the captured step leaves no copy node behind)
                 if i == 0:
                     torch.gt(radii, 0, out=seen)
                 else:
@@ -165,9 +203,9 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         over the batch has no per-frame values)."""
         for p_ in learn:
             p_.grad = None
-        opac = raw_opac if raw else torch.sigmoid(raw_opac)
-        ldr, _, radii, _ = model.forward_frames(range(frames), fixed["means3D"], opac, shs, fixed["scales"], fixed["rotations"])
-        if fused_adam:
+        opac = cur["opacities"] if raw else torch.sigmoid(raw_opac)
+        ldr, _, radii, _ = model.forward_frames(range(frames), cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"])
+        if fused_adam and not mcmc:
             torch.gt(radii, 0, out=seen)      # (radii: the maximum over every frame's poses)
         if lambda_dssim > 0:
             # (one fused loss over the [frames, 3, H, W] batch: it averages over every plane, i.e. it is the MEAN of the
@@ -198,20 +236,40 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             captured.check_overflow()
         total = float(losses.sum())
         ps = float((-10.0 * torch.log10(mses.clamp_min(1e-12))).sum())
+        extra = {}
+        if mcmc:
+            # (the two terms are always computed, so that the last entry -- no update follows it -- reports the same loss)
+            terms = regularize(opt, opacity_reg=opacity_reg, scale_reg=scale_reg).tolist()
+            extra = dict(P=int(cur["means3D"].shape[0]), reg_opacity=terms[0], reg_scale=terms[1])
+            total += frames * (terms[0] + terms[1])
         if it < steps:
             g0 = model.log_exposure.grad
             if g0 is not None:
                 g0[0] = 0.0                                    # frame 0's exposure is the gauge
-            if fused_adam:
+            if mcmc:
+                opt.step()                                     # every row: the regularisers act on unseen Gaussians too
+                inject_noise(opt, generator=gen_dev)
+                if it in refine_at:
+                    relocate(opt, generator=gen_dev)
+                    P_now, left = int(cur["means3D"].shape[0]), len(refine_at) - refine_at.index(it)
+                    factor = min(2.0, max(1.0, (cap / P_now) ** (1.0 / left) * (1.0 + 1e-12)))
+                    res = grow(opt, cap_max=cap, factor=factor, generator=gen_dev)
+                    cur.update(res.params)
+                    learn[:len(CLOUD)] = [cur[k] for k in CLOUD]
+            elif fused_adam:
                 opt.step(visibility=seen)
             else:
                 opt.step()
         e_dt, e_pose = errors()
-        hist.append(dict(step=it, loss=total / frames, psnr=ps / frames, exposure_log_err=e_dt, knot_pos_err=e_pose))
+        hist.append(dict(step=it, loss=total / frames, psnr=ps / frames, exposure_log_err=e_dt, knot_pos_err=e_pose, **extra))
         if not quiet and (it % log_every == 0 or it == steps):
             print(f"step {it:4d}  {'L1' if lambda_dssim == 0 else 'loss'} {total / frames:.5f}  PSNR {ps / frames:6.2f} dB  |log dt - truth| {e_dt:.4f}  "
-                  f"knot position error {e_pose:.5f}  ({(time.time() - t0) / max(it, 1) * 1e3:.1f} ms/step)")
-    return dict(first=hist[0], last=hist[-1], history=hist)
+                  f"knot position error {e_pose:.5f}  ({(time.time() - t0) / max(it, 1) * 1e3:.1f} ms/step)" +
+                  (f"  P {extra['P']}  regularisers {extra['reg_opacity']:.5f} + {extra['reg_scale']:.5f}" if mcmc else ""))
+    out = dict(first=hist[0], last=hist[-1], history=hist)
+    if mcmc:
+        out["cloud"] = {k: cur[k].detach() for k in CLOUD}
+    return out
 
 
 def main(argv=None):
@@ -236,9 +294,18 @@ def main(argv=None):
     ap.add_argument("--batch-frames", action="store_true",
                     help="render all frames of a step in ONE rasterizer call (settings.n_frames; HDRBlurFormation.forward_frames) "
                          "instead of one call per frame; eager only (not with --graph)")
+    ap.add_argument("--mcmc", action="store_true",
+                    help="learn the whole cloud (positions, opacities, radiance, scales, rotations) from P / 4 noised points under "
+                         "the MCMC policy: regularize, step, inject_noise every step, relocate + grow every --refine-every steps; "
+                         "implies --fused-adam --raw; eager only (not with --graph)")
+    ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
+    ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
+    ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
+    ap.add_argument("--scale-reg", type=float, default=0.01, help="--mcmc: weight of mean|scale| (0.01 upstream)")
     a = ap.parse_args(argv)
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
-            fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames)
+            fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
+            refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

@@ -682,6 +682,54 @@ HS_API int hs_mcmc_sample(const hs_mcmc_args* args, void* hip_stream);
 HS_API int hs_mcmc_update(const hs_mcmc_args* args, void* hip_stream);
 HS_API int hs_mcmc_noise(const hs_mcmc_noise_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) The regularisers of the MCMC policy (mcmc_reg.hip): the publication adds
+ *     lambda_o mean|opacity| + lambda_s mean|scale|        (activated values; 0.01 each upstream)
+ * to every step's loss, so that Gaussians die and the relocation has rows to move.  hs_mcmc_regularize is called after
+ * hs_backward and before hs_adam_step: it ADDS the gradient of the two terms, with respect to the values AS STORED, in place
+ * to the gradient rows that exist already -- the rows keep their address -- and optionally writes the two terms to the
+ * device.  No host wait, no allocation, no memset or copy, no atomics; the caller owns every byte.
+ *
+ * fp32 throughout, every operation one correctly rounded IEEE operation plus the library expf, nothing contracted, denormals
+ * kept.  The host computes, in double and rounded once,  ko = (float)(lambda_opacity / P),  ks = (float)(lambda_scale / (3 P)).
+ * Per element (x the stored value, g its gradient):
+ *     opacities, HS_DENSIFY_RAW_OPACITY:   o = 1 / (1 + expf(-x));   g <- g + ko * ((1 - o) * o)     (torch's sigmoid backward)
+ *     opacities, stored linear:            g <- g + ko * sign(x)      sign(+-0) = 0, sign(NaN) = NaN
+ *     scales, HS_DENSIFY_RAW_SCALES:       s = expf(x);              g <- g + ks * s
+ *     scales, stored linear:               g <- g + ks * sign(x)
+ * A gradient array whose lambda is 0 is NOT WRITTEN (its bits stay, -0.0 and NaN included) and may be NULL; with both lambdas
+ * 0 and loss == NULL nothing is launched.  A NaN input gives a NaN in its own element only.
+ * loss (device, [2], or NULL): each element's o or |x| (s or |x| for the scales) -- the fp32 value above -- is converted to
+ * double; a workgroup of 256 Gaussians adds its 256 opacity terms and 768 scale terms (thread t: scale floats t, t + 256,
+ * t + 512 of the block, in that order; then a halving tree over the threads) into one {S_o, S_s} record of the workspace; ONE
+ * workgroup of a second kernel adds the records: thread t those of [t c, (t + 1) c), c = ceil(blocks / 256), ascending, then
+ * thread 0 the 256 thread sums, ascending.
+ *     loss[0] = (float)(lambda_opacity * (S_o / P)),   loss[1] = (float)(lambda_scale * (S_s / (3 P)))
+ * The order is a function of P alone and every record is written before it is read: the same bits on every run, whatever
+ * the workspace held.  Workspace: hs_mcmc_reg_workspace_bytes(P) = align256(16 ceil(P / 256)) bytes, 16-byte aligned, only
+ * read / written when loss != NULL.
+ * One thread covers one opacity and three scale floats; the map is elementwise, so a wave's loads and stores are contiguous.
+ * Limits (HS_EINVAL, reported before any HIP call): 0 <= P < 2^30; flags within HS_DENSIFY_RAW_*; both lambdas finite and
+ * >= 0; opacities / scales non-NULL when their lambda is not 0 or loss is given, a gradient array non-NULL when its lambda is
+ * not 0, workspace non-NULL with loss.  Pointers need 4-byte alignment only (the workspace 16).  With P == 0 loss receives
+ * {0, 0} and no data pointer is looked at. */
+typedef struct hs_mcmc_reg_args {
+    int64_t P;
+    int32_t flags;                /* HS_DENSIFY_RAW_* */
+    int32_t reserved;
+    double lambda_opacity;        /* >= 0, finite */
+    double lambda_scale;          /* >= 0, finite */
+    const float* opacities;       /* [P]     as stored */
+    const float* scales;          /* [P, 3]  as stored */
+    float* dL_dopacities;         /* [P]     in place; may be NULL when lambda_opacity == 0 */
+    float* dL_dscales;            /* [P, 3]  in place; may be NULL when lambda_scale == 0 */
+    float* loss;                  /* device [2] or NULL: {lambda_o mean|o|, lambda_s mean|s|} */
+    void* workspace;              /* hs_mcmc_reg_workspace_bytes(P) bytes, 16-byte aligned; only read / written when loss != NULL */
+} hs_mcmc_reg_args;
+
+/* the formula above; -1 (HS_EINVAL) unless 0 <= P < 2^30 */
+HS_API int64_t hs_mcmc_reg_workspace_bytes(int64_t P);
+HS_API int hs_mcmc_regularize(const hs_mcmc_reg_args* args, void* hip_stream);
+
 /* (detected by name; HS_VERSION unchanged) Activations of the STORED cloud (activate.hip).  A trainer stores logit opacities,
  * log scales and unnormalised quaternions -- what hs_adam_step updates and hs_densify_* compact -- while hs_forward /
  * hs_backward take opacities, scales and unit quaternions.  hs_activate computes the second from the first; hs_activate_backward
