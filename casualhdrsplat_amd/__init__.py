@@ -6,7 +6,8 @@ that consumes its images (losses.photometric_loss, losses.ssim) and the fused, v
 Adam step that applies the gradients (optim.GaussianAdam), and the densify / prune of the cloud that
 changes the number of Gaussians under that optimizer (densify.densify_and_prune), and the neighbour
 distances that size a new cloud (knn.knn_mean_dist2, scene_io.init_from_points), and the MCMC policy's
-relocation, growth, position noise and regularisers (mcmc.relocate, mcmc.grow, mcmc.inject_noise, mcmc.regularize).  Compute lives in
+relocation, growth, position noise and regularisers (mcmc.relocate, mcmc.grow, mcmc.inject_noise, mcmc.regularize), and the
+3D smoothing filter of Mip-Splatting (smoothing.compute_filter_3D, GaussianRasterizer(..., filter_3D=...)).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
@@ -18,9 +19,11 @@ from .mcmc import GrowResult, RelocateResult, grow, inject_noise, regularize, re
 from .optim import GaussianAdam, cloud_param_groups
 from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSettings, GaussianRasterizer,
                          SortChainStalled, inspect_state, rasterize_gaussians)
+from .smoothing import apply_filter_3D, compute_filter_3D
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats", "BinningOverflow", "SortChainStalled",
            "rasterize_gaussians", "inspect_state", "photometric_loss", "ssim", "GaussianAdam", "cloud_param_groups",
            "densify_and_prune", "DensifyResult", "knn_mean_dist2",
-           "relocate", "grow", "inject_noise", "regularize", "RelocateResult", "GrowResult"]
+           "relocate", "grow", "inject_noise", "regularize", "RelocateResult", "GrowResult",
+           "compute_filter_3D", "apply_filter_3D"]
 __version__ = "0.1.0"

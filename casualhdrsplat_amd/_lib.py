@@ -168,6 +168,17 @@ class hs_mcmc_reg_args(C.Structure):
                 ("loss", _fp), ("workspace", _fp)]
 
 
+class hs_smoothing_filter_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("C", C.c_int64), ("xyz", _fp), ("viewmatrices", _fp), ("intrinsics", _fp),
+                ("filter", _fp), ("n_views", _fp), ("workspace", _fp)]
+
+
+class hs_smoothing_apply_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("g_begin", C.c_int64), ("g_end", C.c_int64),
+                ("opacity_raw", _fp), ("scales_raw", _fp), ("filter", _fp), ("opacities", _fp), ("scales", _fp),
+                ("dL_dopacities", _fp), ("dL_dscales", _fp)]
+
+
 EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
            "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
            "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
@@ -176,7 +187,8 @@ EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward"
            "hs_activate", "hs_activate_backward", "hs_max_frames",
            "hs_knn_workspace_bytes", "hs_knn_mean_dist_sq",
            "hs_mcmc_workspace_bytes", "hs_mcmc_sample", "hs_mcmc_update", "hs_mcmc_noise",
-           "hs_mcmc_reg_workspace_bytes", "hs_mcmc_regularize")
+           "hs_mcmc_reg_workspace_bytes", "hs_mcmc_regularize",
+           "hs_smoothing_filter_workspace_bytes", "hs_smoothing_filter", "hs_smoothing_apply", "hs_smoothing_apply_backward")
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a
 # library without it reads hs_dims.n_frames as the reserved word it was and would render all poses into ONE image, silently
 # -- max_frames() is what a request for frames is checked against
@@ -266,6 +278,14 @@ def load() -> C.CDLL:
     lib.hs_mcmc_reg_workspace_bytes.restype = C.c_int64
     lib.hs_mcmc_regularize.argtypes = [C.POINTER(hs_mcmc_reg_args), C.c_void_p]
     lib.hs_mcmc_regularize.restype = C.c_int
+    lib.hs_smoothing_filter_workspace_bytes.argtypes = [C.c_int64]
+    lib.hs_smoothing_filter_workspace_bytes.restype = C.c_int64
+    lib.hs_smoothing_filter.argtypes = [C.POINTER(hs_smoothing_filter_args), C.c_void_p]
+    lib.hs_smoothing_filter.restype = C.c_int
+    lib.hs_smoothing_apply.argtypes = [C.POINTER(hs_smoothing_apply_args), C.c_void_p]
+    lib.hs_smoothing_apply.restype = C.c_int
+    lib.hs_smoothing_apply_backward.argtypes = [C.POINTER(hs_smoothing_apply_args), C.c_void_p]
+    lib.hs_smoothing_apply_backward.restype = C.c_int
     if hasattr(lib, "hs_max_frames"):
         lib.hs_max_frames.argtypes = []
         lib.hs_max_frames.restype = C.c_int

@@ -335,6 +335,16 @@ class HDRBlurFormation(nn.Module):
         return (w2c.transpose(1, 2).reshape(F, n, 4, 4).contiguous(), full.transpose(1, 2).reshape(F, n, 4, 4).contiguous(),
                 campos.reshape(F, n, 3).contiguous())
 
+    def compute_filter_3D(self, means3D: torch.Tensor, return_views: bool = False):
+        """The 3D smoothing filter of Mip-Splatting for this capture (smoothing.compute_filter_3D): over EVERY virtual pose of
+        every frame (cameras_all(): a hand-held camera's nearest approach to a Gaussian may lie inside an exposure window), with
+        fx = W / (2 tanfovx), fy = H / (2 tanfovy).  One launch pair, under no_grad."""
+        from .smoothing import compute_filter_3D
+        with torch.no_grad():
+            views = self.cameras_all()[0].to(torch.float32)
+        return compute_filter_3D(means3D.detach(), views, self.W / (2.0 * self.tanfovx), self.H / (2.0 * self.tanfovy),
+                                 self.W, self.H, return_views=return_views)
+
     def forward(self, i: int, means3D, opacities, shs, scales, rotations, bg=None, cameras=None):
         """`cameras`: the result of cameras_all() (frame i takes its slice) instead of a spline pass of its own."""
         V, PV, Cp = self.cameras(i) if cameras is None else (cameras[0][i], cameras[1][i], cameras[2][i])

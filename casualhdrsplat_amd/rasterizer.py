@@ -293,6 +293,33 @@ def _activate(P: int, op_raw, sc_raw, ro_raw, dev):
     return op, sc, ro
 
 
+def _activate_filtered(P: int, op_raw, sc_raw, ro_raw, filter_3D, dev):
+    """parameterization="raw" with a 3D smoothing filter (smoothing.py): opacities and scales through hs_smoothing_apply --
+    s' = sqrt(exp(l)^2 + f^2), o' = sigmoid(x) sqrt(prod_k exp(l_k)^2 / s'_k^2) -- and only the rotations through
+    hs_activate; two kernels, scratch tensors of the stored tensors' shapes."""
+    if dev.type != "cuda":
+        raise RuntimeError(_NEEDS_GPU)
+    for name, t, cols in (("opacities", op_raw, 1), ("scales", sc_raw, 3), ("rotations", ro_raw, 4)):
+        if t is None or t.numel() != P * cols:
+            raise ValueError(f"parameterization='raw' with filter_3D: {name} has {0 if t is None else t.numel()} elements, "
+                             f"expected {P} x {cols}")
+    op = _empty(tuple(op_raw.shape), torch.float32, dev, "opacities")
+    sc = _empty(tuple(sc_raw.shape), torch.float32, dev, "scales")
+    ro = _empty(tuple(ro_raw.shape), torch.float32, dev, "rotations")
+    if P > 0:
+        lib = L.load()
+        s = L.hs_smoothing_apply_args()
+        s.P = P
+        s.opacity_raw, s.scales_raw, s.filter = _ptr(op_raw), _ptr(sc_raw), _ptr(filter_3D)
+        s.opacities, s.scales = _ptr(op), _ptr(sc)
+        L.check(lib.hs_smoothing_apply(C.byref(s), _stream()), "hs_smoothing_apply")
+        a = L.hs_activate_args()
+        a.P = P
+        a.rotations_raw, a.rotations = _ptr(ro_raw), _ptr(ro)
+        L.check(lib.hs_activate(C.byref(a), _stream()), "hs_activate")
+    return op, sc, ro
+
+
 def _run_forward(settings: GaussianRasterizationSettings, means3D, opacities, shs, colors_precomp, scales,
                  rotations, cov3D_precomp, exposure, crf_table, capacity: Optional[int], want_invdepth: bool = False):
     dev = means3D.device
@@ -485,7 +512,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         with _on_device(dev):  # kernels are launched on the tensors' GPU, whatever the current device is
             if aux is not None and aux.get("raw"):
                 raw = (op, sc, ro)
-                op, sc, ro = _activate(m3.shape[0], op, sc, ro, dev)
+                if aux.get("filter_3D") is not None:
+                    op, sc, ro = _activate_filtered(m3.shape[0], op, sc, ro, aux["filter_3D"], dev)
+                else:
+                    op, sc, ro = _activate(m3.shape[0], op, sc, ro, dev)
             color, hdr, radii, st, exp_t, crf_t, invd = _run_forward(raster_settings, m3, op, shs, cp, sc, ro, cv,
                                                                      exposure, crf_table, capacity, return_invdepth)
         ctx.st = st
@@ -526,6 +556,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.has = (shs is not None, cp is not None, sc is not None, cv is not None, exposure is not None,
                    crf_table is not None)
         ctx.raw = raw is not None
+        ctx.filter_3D = aux.get("filter_3D") if raw is not None else None   # (a constant of the step: no gradient)
         ctx.save_for_backward(m3, op, shs, cp, sc, ro, cv, exp_t, crf_t, *(raw or ()))
         ctx.mark_non_differentiable(radii)
         ctx.n_out = (hdr is not None, bool(return_alpha), bool(return_invdepth))
@@ -560,7 +591,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         want_pose = any(ctx.needs_input_grad[10:13])
         with _on_device(dev):
             g = _launch_backward(st, saved[:9], gcol, ghdr, L.HS_BWD_ALL, want_pose, galpha,
-                                 raw=saved[9:12] if ctx.raw else None, defer_sh=ctx.deferred is not None, ginvd=ginvd, densify=ctx.densify,
+                                 raw=saved[9:12] if ctx.raw else None, filter_3D=ctx.filter_3D, defer_sh=ctx.deferred is not None, ginvd=ginvd, densify=ctx.densify,
                                  gather_group=None if ctx.deferred is None else ctx.deferred.get("gather_group"),
                                  gather_direct=bool(ctx.deferred.get("gather_direct")) if ctx.deferred else False,
                                  reduce_group=None if ctx.aux is None else ctx.aux.get("reduce_group"),
@@ -620,7 +651,7 @@ class _RasterizeGaussians(torch.autograd.Function):
 def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bool = False, galpha=None,
                      defer_sh: bool = False, ginvd=None, densify=None, gather_group=None, stats=None,
                      timeline=None, gather_direct: bool = False, reduce_group=None, reduce_chunks: int = 0,
-                     raw=None) -> dict:
+                     raw=None, filter_3D=None) -> dict:
     """Enqueue hs_backward.  All per-Gaussian gradients are carved out of ONE flat fp32 buffer (the
     layout casualhdrsplat_amd.distributed all-reduces in a single RCCL call): [means3D | opacities | colors | scales |
     rotations | cov3D | exposure | crf_table | sh | means2D | pose gradients].  means2D -- the screen-space
@@ -631,7 +662,8 @@ def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bo
     slices are converted in place to gradients with respect to the stored tensors (hs_activate_backward), directly behind
     the kernels that write them -- per chunk of Gaussians where the backward runs in chunks, BEFORE the chunk's collective
     starts: the conversion is linear and every rank holds the same parameters, so the sum of converted rows is the
-    converted sum."""
+    converted sum.  With `filter_3D` (the flat [P] filter of the forward) the opacities / scales slices go through
+    hs_smoothing_apply_backward instead, over the same rows, and hs_activate_backward converts the rotations only."""
     lib = L.load()
     m3, op, shs, cp, sc, ro, cv, exp_t, crf_t = saved
     dev = m3.device
@@ -696,10 +728,20 @@ def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bo
         b.rotations_raw = _ptr(raw[2])
         b.opacities, b.scales, b.rotations = _ptr(op), _ptr(sc), _ptr(ro)
         b.dL_dopacities, b.dL_dscales, b.dL_drotations = _ptr(g["opacities"]), _ptr(g["scales"]), _ptr(g["rotations"])
+        f = None
+        if filter_3D is not None:
+            b.dL_dopacities, b.dL_dscales = None, None      # (those two tensors: hs_smoothing_apply_backward)
+            f = L.hs_smoothing_apply_args()
+            f.P = P
+            f.opacity_raw, f.scales_raw, f.filter = _ptr(raw[0]), _ptr(raw[1]), _ptr(filter_3D)
+            f.dL_dopacities, f.dL_dscales = _ptr(g["opacities"]), _ptr(g["scales"])
 
         def to_stored(g0, g1):
             b.g_begin, b.g_end = int(g0), int(g1)
             L.check(lib.hs_activate_backward(C.byref(b), _stream()), "hs_activate_backward")
+            if f is not None:
+                f.g_begin, f.g_end = int(g0), int(g1)
+                L.check(lib.hs_smoothing_apply_backward(C.byref(f), _stream()), "hs_smoothing_apply_backward")
 
     if densify is not None:
         if densify.grad_accum.shape[0] != P or densify.grad_accum.device != dev:
@@ -866,7 +908,8 @@ class GaussianRasterizer(nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings, capacity: Optional[int] = None,
                  return_alpha: bool = False, defer_sh_grad: bool = False, return_invdepth: bool = False,
                  densify_stats: Optional[DensifyStats] = None, gather_group=None, keep_state: bool = False,
-                 reduce_group=None, reduce_chunks: int = 4, parameterization: str = "activated"):
+                 reduce_group=None, reduce_chunks: int = 4, parameterization: str = "activated",
+                 filter_3D: Optional[torch.Tensor] = None):
         super().__init__()
         # extension: "raw" = forward() takes opacities, scales and rotations AS A TRAINER STORES THEM -- logits, logs,
         # unnormalised quaternions: the tensors optim.GaussianAdam updates and densify_and_prune compacts -- activates them
@@ -877,6 +920,15 @@ class GaussianRasterizer(nn.Module):
         if parameterization not in PARAMETERIZATIONS:
             raise ValueError(f"parameterization must be one of {PARAMETERIZATIONS}, got {parameterization!r}")
         self.parameterization = parameterization
+        # extension (parameterization="raw" only): the 3D smoothing filter of Mip-Splatting, a contiguous float32 [P] or
+        # [P, 1] tensor (smoothing.compute_filter_3D).  Opacities and scales then go through hs_smoothing_apply /
+        # hs_smoothing_apply_backward -- s' = sqrt(s^2 + f^2), o' = o sqrt(prod s^2 / s'^2) -- and only the rotations through
+        # hs_activate.  A plain attribute: a trainer swaps it after every refinement (forward() checks it on every call);
+        # None = the rasterizer launches exactly what it launches without one.
+        if filter_3D is not None and parameterization != "raw":
+            raise ValueError("filter_3D needs parameterization='raw': the filter is folded into the activations of the "
+                             "stored opacities and scales")
+        self.filter_3D = filter_3D
         # view-parallel training with the plain exchange (every rank renders its own view; the per-Gaussian gradients
         # are summed over the ranks): a torch.distributed process group (or True for the default group) makes the
         # backward run its per-Gaussian half in `reduce_chunks` ascending chunks and start the all-reduce of each
@@ -953,6 +1005,15 @@ class GaussianRasterizer(nn.Module):
         if frames_of(rs) > 1 and (self.return_alpha or self.return_invdepth):
             raise ValueError("return_alpha / return_invdepth are per-image outputs and are not supported with n_frames > 1: "
                              "render those frames one call each")
+        filter_3D = None
+        if self.filter_3D is not None:
+            from .smoothing import check_filter_3D
+            if self.parameterization != "raw":
+                raise ValueError("filter_3D needs parameterization='raw': the filter is folded into the activations of the "
+                                 "stored opacities and scales")
+            if cov3D_precomp is not None:
+                raise ValueError("filter_3D cannot be combined with cov3D_precomp: the filter widens the scales")
+            filter_3D = check_filter_3D(self.filter_3D, int(means3D.shape[0]), means3D.device)
         given = [t for t in (means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp,
                              rs.exposure, rs.crf_table, rs.viewmatrix, rs.projmatrix, rs.campos, rs.viewmatrices,
                              rs.projmatrices, rs.camposes) if isinstance(t, torch.Tensor)]
@@ -974,6 +1035,8 @@ class GaussianRasterizer(nn.Module):
             aux = {"keep_state": self.keep_state, "cell": self._cell}
             if self.parameterization == "raw":
                 aux["raw"] = True
+                if filter_3D is not None:
+                    aux["filter_3D"] = filter_3D
             if self.reduce_group is not None and not self.defer_sh_grad:
                 aux["reduce_group"], aux["reduce_chunks"] = self.reduce_group, self.reduce_chunks
             outs = rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,

@@ -13,7 +13,7 @@ from __future__ import annotations
 import math
 import struct
 from dataclasses import dataclass
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -63,14 +63,29 @@ def _property_names(M: int):
     return names
 
 
-def save_ply(path: str, cloud: GaussianCloud) -> None:
+def _fused(cloud: GaussianCloud, filter_3D: torch.Tensor):
+    """(opacity logits [P, 1], log scales [P, 3]) of the cloud with the 3D smoothing filter folded in (the published
+    save_fused_ply): hs_smoothing_apply on the filter's device, then the inverse activations."""
+    from .smoothing import apply_filter_3D
+    dev = filter_3D.device
+    P = cloud.means3D.shape[0]
+    x = cloud.opacity_logit.detach().to(device=dev, dtype=torch.float32).reshape(P, 1).contiguous()
+    l = cloud.log_scales.detach().to(device=dev, dtype=torch.float32).reshape(P, 3).contiguous()
+    o, s = apply_filter_3D(x, l, filter_3D)
+    return torch.log(o) - torch.log1p(-o), torch.log(s)
+
+
+def save_ply(path: str, cloud: GaussianCloud, filter_3D: Optional[torch.Tensor] = None) -> None:
+    """`filter_3D` (smoothing.compute_filter_3D's result, on the GPU): write the FUSED cloud -- scales sqrt(s^2 + f^2) and
+    opacities o sqrt(prod s^2 / (s^2 + f^2)), as logs and logits -- so that an ordinary viewer draws what was trained."""
+    opacity_logit, log_scales = (cloud.opacity_logit, cloud.log_scales) if filter_3D is None else _fused(cloud, filter_3D)
     m = cloud.means3D.detach().cpu().numpy().astype(np.float32)
     sh = cloud.shs.detach().cpu().numpy().astype(np.float32)
     P, M = sh.shape[0], sh.shape[1]
     cols = [m, np.zeros((P, 3), np.float32), sh[:, 0, :],
             np.transpose(sh[:, 1:, :], (0, 2, 1)).reshape(P, 3 * (M - 1)),  # channel-major rest
-            cloud.opacity_logit.detach().cpu().numpy().astype(np.float32).reshape(P, 1),
-            cloud.log_scales.detach().cpu().numpy().astype(np.float32),
+            opacity_logit.detach().cpu().numpy().astype(np.float32).reshape(P, 1),
+            log_scales.detach().cpu().numpy().astype(np.float32),
             cloud.rotations.detach().cpu().numpy().astype(np.float32)]
     table = np.ascontiguousarray(np.concatenate(cols, axis=1), dtype="<f4")
     names = _property_names(M)

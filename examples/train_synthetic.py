@@ -14,6 +14,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --fused-adam --raw     # the stored (logit) opacities go straight into the rasterizer
     python examples/train_synthetic.py --steps 300 --batch-frames         # all frames of a step in ONE rasterizer call
     python examples/train_synthetic.py --steps 300 --mcmc                 # learn the WHOLE cloud from a quarter of the points: MCMC policy
+    python examples/train_synthetic.py --steps 300 --mcmc --filter-3d     # ... with the 3D smoothing filter of Mip-Splatting
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -63,7 +64,7 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
-        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01):
+        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -84,7 +85,13 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     every row, inject_noise; every `refine_every` steps, from the first such step to steps - refine_every, relocate (dead
     rows onto live ones) and grow towards `cap_max` (default P) by the factor, at most 2, that reaches the budget at the
     last refinement.  Implies fused_adam and raw; eager only (P changes: not with graph=True).  The history gains P and the
-    two regulariser terms, and the reported loss is the mean per-frame loss plus the two terms."""
+    two regulariser terms, and the reported loss is the mean per-frame loss plus the two terms.
+    filter_3d (with mcmc): the 3D smoothing filter of Mip-Splatting.  HDRBlurFormation.compute_filter_3D computes it from every
+    virtual pose of the learner's trajectory at the start and again after every grow (the rows moved and P changed), and the
+    learner's rasterizers fold it into the opacities and scales they run on (GaussianRasterizer.filter_3D); the optimizer, the
+    regularisers and the relocation keep working on the stored tensors.  The history gains the filter's length."""
+    if filter_3d and not mcmc:
+        raise ValueError("filter_3d=True (--filter-3d) needs mcmc=True (--mcmc): the other modes hold the scales at the truth")
     if mcmc and graph:
         raise ValueError("mcmc=True (--mcmc) is not supported together with graph=True (--graph): the number of Gaussians "
                          "changes at every refinement, a captured step is recorded for one size")
@@ -119,6 +126,10 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     how = {"parameterization": "raw"} if raw else {}
     per_frame = FrameRasterizers(capacity=capacity or 40 * P * virtual, **how) if graph else None
     factory = per_frame if graph else (functools.partial(GaussianRasterizer, **how) if raw else None)
+    filt = {"filter_3D": None}          # --filter-3d: the filter of the moment, handed to every rasterizer the learner makes
+    if filter_3d:
+        def factory(settings):
+            return GaussianRasterizer(settings, filter_3D=filt["filter_3D"], **how)
     model = formation(ImplicitCRF(K=128), **({"rasterizer_factory": factory} if factory is not None else {}))
     model.crf.load_state_dict(truth.crf.state_dict())
     for p_ in model.crf.parameters():
@@ -151,6 +162,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         cap = int(cap_max) if cap_max else P
         refine_at = [it for it in range(refine_every, steps - refine_every + 1, refine_every)] if refine_every > 0 else []
         gen_dev = torch.Generator(device=dev).manual_seed(seed + 3)
+        if filter_3d:
+            filt["filter_3D"] = model.compute_filter_3D(cur["means3D"])
     elif fused_adam:
         opt = GaussianAdam([
             {"params": [shs], "lr": 1e-2, "per_gaussian": True}, {"params": [raw_opac], "lr": 2e-2, "per_gaussian": True},
@@ -242,6 +255,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             terms = regularize(opt, opacity_reg=opacity_reg, scale_reg=scale_reg).tolist()
             extra = dict(P=int(cur["means3D"].shape[0]), reg_opacity=terms[0], reg_scale=terms[1])
             total += frames * (terms[0] + terms[1])
+            if filter_3d:
+                extra["filter_len"] = int(filt["filter_3D"].shape[0])
         if it < steps:
             g0 = model.log_exposure.grad
             if g0 is not None:
@@ -256,6 +271,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                     res = grow(opt, cap_max=cap, factor=factor, generator=gen_dev)
                     cur.update(res.params)
                     learn[:len(CLOUD)] = [cur[k] for k in CLOUD]
+                    if filter_3d:                              # (the rows moved and P changed: the filter follows)
+                        filt["filter_3D"] = model.compute_filter_3D(cur["means3D"])
             elif fused_adam:
                 opt.step(visibility=seen)
             else:
@@ -269,6 +286,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     out = dict(first=hist[0], last=hist[-1], history=hist)
     if mcmc:
         out["cloud"] = {k: cur[k].detach() for k in CLOUD}
+        if filter_3d:
+            out["filter_3D"] = filt["filter_3D"]
     return out
 
 
@@ -298,6 +317,9 @@ def main(argv=None):
                     help="learn the whole cloud (positions, opacities, radiance, scales, rotations) from P / 4 noised points under "
                          "the MCMC policy: regularize, step, inject_noise every step, relocate + grow every --refine-every steps; "
                          "implies --fused-adam --raw; eager only (not with --graph)")
+    ap.add_argument("--filter-3d", action="store_true",
+                    help="--mcmc: the 3D smoothing filter of Mip-Splatting, computed from every virtual pose at the start and after "
+                         "every grow and folded into the opacities and scales the rasterizers run on")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
@@ -305,7 +327,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
-            refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg)
+            refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

@@ -770,6 +770,80 @@ typedef struct hs_activate_args {
 HS_API int hs_activate(const hs_activate_args* args, void* hip_stream);
 HS_API int hs_activate_backward(const hs_activate_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) The 3D smoothing filter of Mip-Splatting (smoothing.hip).  HS_FLAG_ANTIALIAS is the
+ * publication's 2D screen-space filter; this is its per-Gaussian half: a radius, from the training cameras, below which no
+ * camera resolves a Gaussian (hs_smoothing_filter), and the activations of the stored cloud with that radius folded into the
+ * scales and opacities (hs_smoothing_apply / hs_smoothing_apply_backward, in place of hs_activate / hs_activate_backward for
+ * those two tensors).  Kernels only, on the caller's stream: no memset, no copy, no allocation, no synchronisation, no
+ * floating-point atomics; the caller owns every byte.  fp32, every operation one correctly rounded IEEE operation plus the
+ * library expf, nothing contracted, denormals kept: the same inputs give the same bits on every run.
+ *
+ * hs_smoothing_filter.  Per Gaussian i (x, y, z its position) and camera c, with m the camera's 16 floats (the transposed
+ * convention of hs_fwd_args.viewmatrices) and (fx, fy, W, H) its intrinsics in pixels:
+ *     xc = ((m0 x + m4 y) + m8 z) + m12;   yc = ((m1 x + m5 y) + m9 z) + m13;   zc = ((m2 x + m6 y) + m10 z) + m14
+ *     u  = (xc / zc) * fx + 0.5f * W;      v  = (yc / zc) * fy + 0.5f * H
+ *     valid = zc > 0.2f && u >= -0.15f * W && u <= 1.15f * W && v >= -0.15f * H && v <= 1.15f * H       (a NaN: not valid)
+ * (the published margin and near plane; 0.2 is also the rasterizer's cull).  d_i = the minimum of zc over the valid cameras,
+ * n_i = their number; D = the maximum of d_i over the Gaussians with n_i > 0; fmax = the maximum of fx over all cameras (a NaN
+ * fx is passed over).  Then
+ *     filter[i] = ((n_i > 0 ? d_i : D) / fmax) * 0.4472135901451111f          (sqrt(0.2) in fp32, bits 0x3ee4f92e)
+ * -- a Gaussian no camera sees takes the largest seen distance, as published.  If no Gaussian is seen at all, or C == 0, every
+ * filter[i] is 0.0f and every n_i is 0.  Minimum and maximum are exact in any order, so the result does not depend on how the
+ * kernels divide the work.  Two launches: one thread per Gaussian with the cameras staged through LDS 64 at a time, one
+ * {D_b, fmax} pair of workspace words per workgroup; then every workgroup folds the pairs and writes the radii.  Nothing at
+ * or beyond row P of filter / n_views and nothing beyond hs_smoothing_filter_workspace_bytes(P) bytes of the workspace is
+ * written, and no workspace word is read that this call has not written: the result is the same whatever the workspace held.
+ * Limits (HS_EINVAL, reported before any HIP call): 0 <= P < 2^30; 0 <= C < 2^20; xyz, filter and workspace non-NULL, and with
+ * C > 0 viewmatrices and intrinsics; every pointer 4-byte aligned, the workspace 256-byte aligned.  P == 0 is a successful
+ * no-op: no data pointer is looked at and nothing is launched. */
+typedef struct hs_smoothing_filter_args {
+    int64_t P;                    /* Gaussians */
+    int64_t C;                    /* cameras */
+    const float* xyz;             /* [P, 3] */
+    const float* viewmatrices;    /* [C, 16] transposed convention, as hs_fwd_args.viewmatrices; may be NULL when C == 0 */
+    const float* intrinsics;      /* [C, 4]  (fx, fy, W, H) in pixels, per camera; may be NULL when C == 0 */
+    float* filter;                /* [P] out: the radius */
+    int32_t* n_views;             /* [P] out or NULL: cameras that see the Gaussian */
+    void* workspace;              /* hs_smoothing_filter_workspace_bytes(P) bytes, 256-byte aligned */
+} hs_smoothing_filter_args;
+
+/* align256(8 min(ceil(P / 256), 2048)): a multiple of 256, non-decreasing in P; -1 (HS_EINVAL) unless 0 <= P < 2^30 */
+HS_API int64_t hs_smoothing_filter_workspace_bytes(int64_t P);
+HS_API int hs_smoothing_filter(const hs_smoothing_filter_args* args, void* hip_stream);
+
+/* hs_smoothing_apply, rows [0, P), with x = opacity_raw[i], l_k = scales_raw[3 i + k], f = filter[i]:
+ *     o  = 1 / (1 + expf(-x));   s_k = expf(l_k);   q_k = s_k s_k;   f2 = f f
+ *     v_k = q_k + f2;   s'_k = sqrtf(v_k);   r_k = q_k / v_k;   t_k = f2 / v_k;        where v_k == 0:  r_k = 1, t_k = 0
+ *     c  = sqrtf((r_0 r_1) r_2);   o' = o c
+ *     scales[3 i + k] = s'_k;   opacities[i] = o'
+ * c is the published sqrt(det(S^2) / det(S^2 + f^2 I)) as a product of per-axis ratios, so that tiny scales do not underflow;
+ * t_k is 1 - r_k without the cancellation.  A filter of zeros gives hs_activate's opacities and scales bit for bit.
+ * hs_smoothing_apply_backward, rows [g_begin, g_end), IN PLACE on the gradient rows hs_backward wrote (g_o, g_k the values
+ * found there; every element is read and written by the same thread); o, s', r, t, c and o' are recomputed from the stored
+ * values with the forward's own operations and carry its bits -- opacities / scales are not read:
+ *     dL_dopacities[i]   <- ((g_o c) o) (1 - o)
+ *     dL_dscales[3i + k] <- (g_k s'_k) r_k + (g_o o') t_k          where t_k == 0 the second term is not added
+ * (with a zero filter the rows are hs_activate_backward's bit for bit, a -0.0 included).  The filter is a constant and gets no gradient.  The map is linear in g: converting the rows of a chunk before they are summed
+ * over ranks that hold the same parameters gives the sum's conversion.  A thread takes four consecutive rows; 16-byte accesses
+ * are used where every pointer is 16-byte aligned and the four rows lie inside the range, 4-byte accesses of exactly the rows'
+ * elements otherwise.  Limits (HS_EINVAL, reported before any HIP call): 0 <= P < 2^30, 0 <= g_begin <= g_end <= P; forward:
+ * opacity_raw, scales_raw, filter, opacities, scales non-NULL; backward: opacity_raw, scales_raw, filter, dL_dopacities,
+ * dL_dscales non-NULL; 4-byte alignment.  P == 0 and an empty range are successful no-ops (no pointer is looked at). */
+typedef struct hs_smoothing_apply_args {
+    int64_t P;                    /* rows of every tensor */
+    int64_t g_begin, g_end;       /* hs_smoothing_apply_backward: the rows to convert (hs_smoothing_apply ignores them) */
+    const float* opacity_raw;     /* [P]     logits */
+    const float* scales_raw;      /* [P, 3]  logs */
+    const float* filter;          /* [P]     what hs_smoothing_filter wrote (any non-negative radius) */
+    float* opacities;             /* [P]     written by hs_smoothing_apply */
+    float* scales;                /* [P, 3]  written by hs_smoothing_apply */
+    float* dL_dopacities;         /* [P]     hs_smoothing_apply_backward, in place */
+    float* dL_dscales;            /* [P, 3]  hs_smoothing_apply_backward, in place */
+} hs_smoothing_apply_args;
+
+HS_API int hs_smoothing_apply(const hs_smoothing_apply_args* args, void* hip_stream);
+HS_API int hs_smoothing_apply_backward(const hs_smoothing_apply_args* args, void* hip_stream);
+
 /* (detected by name; HS_VERSION unchanged) Mean squared distance to the three nearest neighbours of every point (knn.hip):
  * the isotropic scale of the published SfM initialisation (upstream: simple_knn.distCUDA2).  For every point i of xyz [P, 3],
  * over all j != i -- excluded BY INDEX, not by distance --
