@@ -179,16 +179,53 @@ class hs_smoothing_apply_args(C.Structure):
                 ("dL_dopacities", _fp), ("dL_dscales", _fp)]
 
 
-EXPORTS = ("hs_version", "hs_last_error", "hs_plan", "hs_forward", "hs_backward", "hs_mark_visible",
-           "hs_sh_backward_views", "hs_sort_tmp_bytes", "hs_sort_pairs", "hs_render_stats", "hs_sort_tickets", "hs_spline_poses", "hs_depth_sort",
-           "hs_loss_workspace_bytes", "hs_photometric_loss", "hs_photometric_loss_backward",
-           "hs_adam_state_bytes", "hs_adam_step",
-           "hs_densify_workspace_bytes", "hs_densify_plan", "hs_densify_apply",
-           "hs_activate", "hs_activate_backward", "hs_max_frames",
-           "hs_knn_workspace_bytes", "hs_knn_mean_dist_sq",
-           "hs_mcmc_workspace_bytes", "hs_mcmc_sample", "hs_mcmc_update", "hs_mcmc_noise",
-           "hs_mcmc_reg_workspace_bytes", "hs_mcmc_regularize",
-           "hs_smoothing_filter_workspace_bytes", "hs_smoothing_filter", "hs_smoothing_apply", "hs_smoothing_apply_backward")
+def _call(args):
+    """int f(const args*, void* hip_stream): the shape of most entry points"""
+    return C.c_int, [C.POINTER(args), C.c_void_p]
+
+
+# Every export of include/hdrsplat.h: name -> (restype, argtypes; None = not declared).  load() sets the signatures from this
+# table and EXPORTS is its keys: a new entry point takes one line here.
+_vp, _i32, _i64 = C.c_void_p, C.c_int32, C.c_int64
+SIGNATURES = {
+    "hs_version": (C.c_int, None),
+    "hs_last_error": (C.c_char_p, None),
+    "hs_plan": (C.c_int, [C.POINTER(hs_dims), C.POINTER(hs_sizes), C.POINTER(hs_layout)]),
+    "hs_forward": _call(hs_fwd_args),
+    "hs_backward": _call(hs_bwd_args),
+    "hs_mark_visible": (C.c_int, [_i32, _vp, _vp, _vp, _vp]),
+    "hs_sh_backward_views": (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "hs_sort_tmp_bytes": (_i64, [_i64]),
+    "hs_sort_pairs": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "hs_render_stats": (C.c_int, [C.POINTER(hs_fwd_args), C.POINTER(hs_bwd_args), _vp, _vp, _vp]),
+    "hs_sort_tickets": (C.c_int, [C.c_int]),
+    "hs_spline_poses": (C.c_int, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hs_depth_sort": (C.c_int, [C.c_int]),
+    "hs_loss_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "hs_photometric_loss": _call(hs_loss_args),
+    "hs_photometric_loss_backward": _call(hs_loss_args),
+    "hs_adam_state_bytes": (_i64, [_i32]),
+    "hs_adam_step": _call(hs_adam_args),
+    "hs_densify_workspace_bytes": (_i64, [_i64]),
+    "hs_densify_plan": _call(hs_densify_args),
+    "hs_densify_apply": _call(hs_densify_args),
+    "hs_activate": _call(hs_activate_args),
+    "hs_activate_backward": _call(hs_activate_args),
+    "hs_max_frames": (C.c_int, []),
+    "hs_knn_workspace_bytes": (_i64, [_i64]),
+    "hs_knn_mean_dist_sq": _call(hs_knn_args),
+    "hs_mcmc_workspace_bytes": (_i64, [_i64, _i64]),
+    "hs_mcmc_sample": _call(hs_mcmc_args),
+    "hs_mcmc_update": _call(hs_mcmc_args),
+    "hs_mcmc_noise": _call(hs_mcmc_noise_args),
+    "hs_mcmc_reg_workspace_bytes": (_i64, [_i64]),
+    "hs_mcmc_regularize": _call(hs_mcmc_reg_args),
+    "hs_smoothing_filter_workspace_bytes": (_i64, [_i64]),
+    "hs_smoothing_filter": _call(hs_smoothing_filter_args),
+    "hs_smoothing_apply": _call(hs_smoothing_apply_args),
+    "hs_smoothing_apply_backward": _call(hs_smoothing_apply_args),
+}
+EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a
 # library without it reads hs_dims.n_frames as the reserved word it was and would render all poses into ONE image, silently
 # -- max_frames() is what a request for frames is checked against
@@ -212,83 +249,15 @@ def load() -> C.CDLL:
     for name in EXPORTS:
         if not hasattr(lib, name) and name not in OPTIONAL_EXPORTS:
             raise RuntimeError(f"{LIB_PATH} does not export {name}")
-    lib.hs_version.restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(lib, name):         # (only an OPTIONAL_EXPORTS name can be missing here)
+            fn = getattr(lib, name)
+            fn.restype = restype
+            if argtypes is not None:
+                fn.argtypes = argtypes
     if lib.hs_version() != HS_VERSION:   # (a stale variant picked by HS_LIB_PATH would read the structs short or long)
         raise RuntimeError(f"{LIB_PATH} is HS_VERSION {lib.hs_version()}, this package mirrors the structs of "
                            f"{HS_VERSION}: rebuild it (`make -C casualhdrsplat_amd/csrc`)")
-    lib.hs_last_error.restype = C.c_char_p
-    lib.hs_plan.argtypes = [C.POINTER(hs_dims), C.POINTER(hs_sizes), C.POINTER(hs_layout)]
-    lib.hs_plan.restype = C.c_int
-    lib.hs_forward.argtypes = [C.POINTER(hs_fwd_args), C.c_void_p]
-    lib.hs_forward.restype = C.c_int
-    lib.hs_backward.argtypes = [C.POINTER(hs_bwd_args), C.c_void_p]
-    lib.hs_backward.restype = C.c_int
-    lib.hs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.hs_mark_visible.restype = C.c_int
-    lib.hs_sh_backward_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p]
-    lib.hs_sh_backward_views.restype = C.c_int
-    lib.hs_render_stats.argtypes = [C.POINTER(hs_fwd_args), C.POINTER(hs_bwd_args), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.hs_render_stats.restype = C.c_int
-    lib.hs_sort_tmp_bytes.argtypes = [C.c_int64]
-    lib.hs_sort_tmp_bytes.restype = C.c_int64
-    lib.hs_sort_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
-                                  C.c_void_p, C.c_void_p]
-    lib.hs_sort_pairs.restype = C.c_int
-    lib.hs_spline_poses.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                    C.c_void_p, C.c_void_p]
-    lib.hs_spline_poses.restype = C.c_int
-    lib.hs_sort_tickets.argtypes = [C.c_int]
-    lib.hs_sort_tickets.restype = C.c_int
-    lib.hs_depth_sort.argtypes = [C.c_int]
-    lib.hs_depth_sort.restype = C.c_int
-    lib.hs_loss_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
-    lib.hs_loss_workspace_bytes.restype = C.c_int64
-    lib.hs_photometric_loss.argtypes = [C.POINTER(hs_loss_args), C.c_void_p]
-    lib.hs_photometric_loss.restype = C.c_int
-    lib.hs_photometric_loss_backward.argtypes = [C.POINTER(hs_loss_args), C.c_void_p]
-    lib.hs_photometric_loss_backward.restype = C.c_int
-    lib.hs_adam_state_bytes.argtypes = [C.c_int32]
-    lib.hs_adam_state_bytes.restype = C.c_int64
-    lib.hs_adam_step.argtypes = [C.POINTER(hs_adam_args), C.c_void_p]
-    lib.hs_adam_step.restype = C.c_int
-    lib.hs_densify_workspace_bytes.argtypes = [C.c_int64]
-    lib.hs_densify_workspace_bytes.restype = C.c_int64
-    lib.hs_densify_plan.argtypes = [C.POINTER(hs_densify_args), C.c_void_p]
-    lib.hs_densify_plan.restype = C.c_int
-    lib.hs_densify_apply.argtypes = [C.POINTER(hs_densify_args), C.c_void_p]
-    lib.hs_densify_apply.restype = C.c_int
-    lib.hs_activate.argtypes = [C.POINTER(hs_activate_args), C.c_void_p]
-    lib.hs_activate.restype = C.c_int
-    lib.hs_activate_backward.argtypes = [C.POINTER(hs_activate_args), C.c_void_p]
-    lib.hs_activate_backward.restype = C.c_int
-    lib.hs_knn_workspace_bytes.argtypes = [C.c_int64]
-    lib.hs_knn_workspace_bytes.restype = C.c_int64
-    lib.hs_knn_mean_dist_sq.argtypes = [C.POINTER(hs_knn_args), C.c_void_p]
-    lib.hs_knn_mean_dist_sq.restype = C.c_int
-    lib.hs_mcmc_workspace_bytes.argtypes = [C.c_int64, C.c_int64]
-    lib.hs_mcmc_workspace_bytes.restype = C.c_int64
-    lib.hs_mcmc_sample.argtypes = [C.POINTER(hs_mcmc_args), C.c_void_p]
-    lib.hs_mcmc_sample.restype = C.c_int
-    lib.hs_mcmc_update.argtypes = [C.POINTER(hs_mcmc_args), C.c_void_p]
-    lib.hs_mcmc_update.restype = C.c_int
-    lib.hs_mcmc_noise.argtypes = [C.POINTER(hs_mcmc_noise_args), C.c_void_p]
-    lib.hs_mcmc_noise.restype = C.c_int
-    lib.hs_mcmc_reg_workspace_bytes.argtypes = [C.c_int64]
-    lib.hs_mcmc_reg_workspace_bytes.restype = C.c_int64
-    lib.hs_mcmc_regularize.argtypes = [C.POINTER(hs_mcmc_reg_args), C.c_void_p]
-    lib.hs_mcmc_regularize.restype = C.c_int
-    lib.hs_smoothing_filter_workspace_bytes.argtypes = [C.c_int64]
-    lib.hs_smoothing_filter_workspace_bytes.restype = C.c_int64
-    lib.hs_smoothing_filter.argtypes = [C.POINTER(hs_smoothing_filter_args), C.c_void_p]
-    lib.hs_smoothing_filter.restype = C.c_int
-    lib.hs_smoothing_apply.argtypes = [C.POINTER(hs_smoothing_apply_args), C.c_void_p]
-    lib.hs_smoothing_apply.restype = C.c_int
-    lib.hs_smoothing_apply_backward.argtypes = [C.POINTER(hs_smoothing_apply_args), C.c_void_p]
-    lib.hs_smoothing_apply_backward.restype = C.c_int
-    if hasattr(lib, "hs_max_frames"):
-        lib.hs_max_frames.argtypes = []
-        lib.hs_max_frames.restype = C.c_int
     if os.environ.get("HS_SORT_TICKETS", "")[:1] == "1":   # the process default of the chain order, set once
         lib.hs_sort_tickets(1)
     _lib = lib

@@ -26,7 +26,7 @@
 // byte outside the rows asked for is read or written.  The three tensors are three SEGMENTS of one grid: a workgroup takes
 // virtual blocks of 256 quads, finds the segment of each from a prefix table in the kernel arguments, and strides over them
 // (the grid is capped at 2048 workgroups).  No LDS, no atomics, no scratch: the same inputs give the same bits.
-#include "hs_common.h"
+#include "hs_cloud.h"
 
 #include <math.h>
 #include <string.h>
@@ -37,8 +37,6 @@ namespace {
 constexpr int kActThreads = 256;
 constexpr int kActMaxGrid = 2048;            // 256 CUs x 8 workgroups; larger problems stride
 constexpr float kNormEps = 1e-12f;           // torch.nn.functional.normalize's clamp
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 enum { kActOpacity = 0, kActScale = 1, kActRotation = 2 };
 
@@ -57,28 +55,6 @@ struct ActLaunch {
     int32_t n_seg;
 };
 
-__device__ __forceinline__ float sigmoid_of(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// the length of the stored quaternion before the clamp (the backward asks whether the clamp was active)
-__device__ __forceinline__ float quat_length(const f4 q) {
-    return sqrtf(((q.x * q.x + q.y * q.y) + q.z * q.z) + q.w * q.w);
-}
-
-__device__ __forceinline__ f4 load_quad(const float* p, bool vec) {
-    if (vec) return *reinterpret_cast<const f4*>(p);
-    f4 v;
-    v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3];
-    return v;
-}
-
-__device__ __forceinline__ void store_quad(float* p, const f4 v, bool vec) {
-    if (vec) {
-        *reinterpret_cast<f4*>(p) = v;
-    } else {
-        p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w;
-    }
-}
-
 // the quad of work item `w` of segment S: its first float e0 and which of its four floats belong to the rows asked for
 __device__ __forceinline__ bool quad_of(const ActSeg& S, int64_t w, int64_t& e0, bool ok[4]) {
     e0 = 4 * (S.first + w);
@@ -90,9 +66,7 @@ __device__ __forceinline__ bool quad_of(const ActSeg& S, int64_t w, int64_t& e0,
 __global__ void __launch_bounds__(kActThreads) activate_fwd_kernel(const ActLaunch L) {
     const uint32_t n_blocks = L.first_block[L.n_seg];
     for (uint32_t vb = blockIdx.x; vb < n_blocks; vb += gridDim.x) {
-        int si = 0;
-#pragma unroll 1
-        for (int i = 1; i < L.n_seg; ++i) si += vb >= L.first_block[i] ? 1 : 0;     // (uniform: scalar loads of the arguments)
+        HS_BLOCK_OWNER(si, vb, L.first_block, L.n_seg);
         const ActSeg& S = L.seg[si];
         const int64_t w = (int64_t)(vb - L.first_block[si]) * kActThreads + threadIdx.x;
         int64_t e0;
@@ -101,7 +75,7 @@ __global__ void __launch_bounds__(kActThreads) activate_fwd_kernel(const ActLaun
         if (e0 >= S.hi) continue;
         if (S.kind == kActRotation) {                 // (a quaternion is wholly inside or wholly outside)
             const f4 q = load_quad(S.raw + e0, S.vec != 0);
-            const float len = quat_length(q);
+            const float len = quat_length(q.x, q.y, q.z, q.w);        // before the clamp
             const float n = len < kNormEps ? kNormEps : len;        // max(len, eps); a NaN stays one, as in torch
             f4 r;
             r.x = q.x / n; r.y = q.y / n; r.z = q.z / n; r.w = q.w / n;
@@ -125,9 +99,7 @@ __global__ void __launch_bounds__(kActThreads) activate_fwd_kernel(const ActLaun
 __global__ void __launch_bounds__(kActThreads) activate_bwd_kernel(const ActLaunch L) {
     const uint32_t n_blocks = L.first_block[L.n_seg];
     for (uint32_t vb = blockIdx.x; vb < n_blocks; vb += gridDim.x) {
-        int si = 0;
-#pragma unroll 1
-        for (int i = 1; i < L.n_seg; ++i) si += vb >= L.first_block[i] ? 1 : 0;
+        HS_BLOCK_OWNER(si, vb, L.first_block, L.n_seg);
         const ActSeg& S = L.seg[si];
         const int64_t w = (int64_t)(vb - L.first_block[si]) * kActThreads + threadIdx.x;
         int64_t e0;
@@ -138,7 +110,7 @@ __global__ void __launch_bounds__(kActThreads) activate_bwd_kernel(const ActLaun
             const f4 q = load_quad(S.raw + e0, S.vec != 0);
             const f4 u = load_quad(S.act + e0, S.vec != 0);
             f4 g = load_quad(S.grad + e0, S.vec != 0);
-            const float n = quat_length(q);
+            const float n = quat_length(q.x, q.y, q.z, q.w);          // (n < eps: the clamp was active)
             if (n < kNormEps) {
                 g.x = g.x / kNormEps; g.y = g.y / kNormEps; g.z = g.z / kNormEps; g.w = g.w / kNormEps;
             } else {
@@ -166,15 +138,13 @@ __global__ void __launch_bounds__(kActThreads) activate_bwd_kernel(const ActLaun
     }
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // rows [r0, r1) of a tensor of `cols` floats per row as a segment; returns its quads
 int64_t make_segment(ActSeg& s, int kind, int64_t cols, int64_t r0, int64_t r1, const float* raw, float* act, float* grad) {
     memset(&s, 0, sizeof(s));
     s.kind = kind;
     s.raw = raw; s.act = act; s.grad = grad;
     s.lo = r0 * cols; s.hi = r1 * cols;
-    s.vec = (!raw || aligned16(raw)) && aligned16(act) && (!grad || aligned16(grad)) ? 1 : 0;
+    s.vec = aligned_to(raw, 16) && aligned_to(act, 16) && aligned_to(grad, 16) ? 1 : 0;      // (a null pointer is one not given)
     s.first = s.lo / 4;
     return (s.hi + 3) / 4 - s.first;
 }

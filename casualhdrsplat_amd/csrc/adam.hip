@@ -35,7 +35,7 @@
 // segment of each from a prefix table, and strides over them (the grid is capped at 2048 workgroups).
 //
 // Visibility: in a masked segment the row's mask entry is read FIRST; rows that are not visible are not loaded, not stored.
-#include "hs_common.h"
+#include "hs_cloud.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -51,8 +51,6 @@ namespace {
 constexpr int kAdamThreads = 256;
 constexpr int kAdamMaxGrid = 2048;           // 256 CUs x 8 workgroups; larger problems stride
 constexpr int kAdamMaxSeg = HS_ADAM_MAX_GROUPS;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct AdamHyp {            // what the tick derives for one group (the tail of its 64-byte state slot)
     float step_size, bc2, b1, b2, omb1, omb2, eps, pad;
@@ -142,18 +140,6 @@ __device__ __forceinline__ bool row_visible(const void* mask, int kind, int64_t 
     return reinterpret_cast<const uint8_t*>(mask)[row] != 0;
 }
 
-// a / b and a % b of non-negative values; `small`: both below 2^32 (a uniform flag: 32-bit division is a fifth of the 64-bit one)
-__device__ __forceinline__ void divmod(int64_t a, int64_t b, bool small, int64_t& q, int64_t& r) {
-    if (small) {
-        const uint32_t qq = (uint32_t)a / (uint32_t)b;
-        q = qq;
-        r = (uint32_t)a - qq * (uint32_t)b;
-    } else {
-        q = a / b;
-        r = a - q * b;
-    }
-}
-
 __device__ __forceinline__ void store_moment(f4* dst, f4 val) {
 #if HS_TUNE_ADAM_NT
     __builtin_nontemporal_store(val, dst);
@@ -165,9 +151,7 @@ __device__ __forceinline__ void store_moment(f4* dst, f4 val) {
 __global__ void __launch_bounds__(kAdamThreads) adam_update_kernel(const AdamLaunch L, const AdamState* __restrict__ st) {
     const uint32_t n_blocks = L.first_block[L.n_seg];
     for (uint32_t vb = blockIdx.x; vb < n_blocks; vb += gridDim.x) {
-        int si = 0;
-#pragma unroll 1
-        for (int i = 1; i < L.n_seg; ++i) si += vb >= L.first_block[i] ? 1 : 0;     // (uniform: scalar loads of the arguments)
+        HS_BLOCK_OWNER(si, vb, L.first_block, L.n_seg);
         const AdamSeg& S = L.seg[si];
         const int64_t w = (int64_t)(vb - L.first_block[si]) * kAdamThreads + threadIdx.x;
         if (w >= S.n_items) continue;
@@ -242,10 +226,6 @@ __global__ void __launch_bounds__(kAdamThreads) adam_update_kernel(const AdamLau
     }
 }
 
-constexpr int64_t kAdamMaxFloats = 1ll << 40;
-
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // the segment of one group (`masked`: the mask applies)
 AdamSeg make_segment(const hs_adam_group& G, int hyp, bool masked) {
     AdamSeg s;
@@ -254,10 +234,10 @@ AdamSeg make_segment(const hs_adam_group& G, int hyp, bool masked) {
     s.hyp_a = s.hyp_b = hyp;
     s.masked = masked ? 1 : 0;
     const int64_t S = G.row_stride, n = G.rows * S;
-    const bool vec = aligned16(G.param) && aligned16(G.exp_avg) && aligned16(G.exp_avg_sq);
+    const bool vec = aligned_to(G.param, 16) && aligned_to(G.exp_avg, 16) && aligned_to(G.exp_avg_sq, 16);
     const bool full = G.col_begin == 0 && G.col_count == S;
     s.small = n < (1ll << 32) ? 1 : 0;
-    s.g_vec = aligned16(G.grad) ? 1 : 0;
+    s.g_vec = aligned_to(G.grad, 16) ? 1 : 0;
     if (vec && full && (!masked || S % 4 != 0)) {
         s.mode = kSegFlat;
         s.row_len = n;
@@ -303,7 +283,7 @@ bool merge_columns(AdamSeg& a, const AdamSeg& b) {
 }
 
 int check_adam_args(const hs_adam_args* a) {
-    if (!a) { set_error("hs_adam_step: null args"); return HS_EINVAL; }
+    if (check_args("hs_adam_step", a)) return HS_EINVAL;
     if (a->n_groups < 1 || a->n_groups > HS_ADAM_MAX_GROUPS) {
         set_error("hs_adam_step: n_groups=%d outside [1, %d]", a->n_groups, HS_ADAM_MAX_GROUPS);
         return HS_EINVAL;
@@ -311,15 +291,15 @@ int check_adam_args(const hs_adam_args* a) {
     if (!a->groups) { set_error("hs_adam_step: null groups"); return HS_EINVAL; }
     if (!a->state) { set_error("hs_adam_step: null state"); return HS_EINVAL; }
     if (!a->hyper) { set_error("hs_adam_step: null hyper"); return HS_EINVAL; }
-    if ((uintptr_t)a->state & 15) { set_error("hs_adam_step: state must be 16-byte aligned"); return HS_EINVAL; }
-    if ((uintptr_t)a->hyper & 7) { set_error("hs_adam_step: hyper must be 8-byte aligned"); return HS_EINVAL; }
+    if (!aligned_to(a->state, 16)) { set_error("hs_adam_step: state must be 16-byte aligned"); return HS_EINVAL; }
+    if (!aligned_to(a->hyper, 8)) { set_error("hs_adam_step: hyper must be 8-byte aligned"); return HS_EINVAL; }
     if (a->mask_kind != HS_ADAM_MASK_NONE && a->mask_kind != HS_ADAM_MASK_RADII && a->mask_kind != HS_ADAM_MASK_BYTES) {
         set_error("hs_adam_step: mask_kind=%d is none of HS_ADAM_MASK_NONE / _RADII / _BYTES", a->mask_kind);
         return HS_EINVAL;
     }
     if (a->mask_len < 0) { set_error("hs_adam_step: mask_len=%lld is negative", (long long)a->mask_len); return HS_EINVAL; }
     if (a->mask_kind != HS_ADAM_MASK_NONE && !a->mask && a->mask_len > 0) { set_error("hs_adam_step: null mask"); return HS_EINVAL; }
-    if (a->mask_kind == HS_ADAM_MASK_RADII && ((uintptr_t)a->mask & 3)) {
+    if (a->mask_kind == HS_ADAM_MASK_RADII && !aligned_to(a->mask, 4)) {
         set_error("hs_adam_step: mask (int32 radii) must be 4-byte aligned");
         return HS_EINVAL;
     }
@@ -336,7 +316,7 @@ int check_adam_args(const hs_adam_args* a) {
                       (long long)G.col_count, (long long)G.row_stride);
             return HS_EINVAL;
         }
-        if (G.rows > 0 && G.row_stride > kAdamMaxFloats / G.rows) {
+        if (G.rows > 0 && G.row_stride > kMaxFloats / G.rows) {
             set_error("hs_adam_step: groups[%d]: rows * row_stride = %lld * %lld exceeds 2^40", i, (long long)G.rows, (long long)G.row_stride);
             return HS_EINVAL;
         }
@@ -350,7 +330,7 @@ int check_adam_args(const hs_adam_args* a) {
             set_error("hs_adam_step: groups[%d]: null param/grad/exp_avg/exp_avg_sq", i);
             return HS_EINVAL;
         }
-        if (((uintptr_t)G.param | (uintptr_t)G.grad | (uintptr_t)G.exp_avg | (uintptr_t)G.exp_avg_sq) & 3) {
+        if (!aligned_to(G.param, 4) || !aligned_to(G.grad, 4) || !aligned_to(G.exp_avg, 4) || !aligned_to(G.exp_avg_sq, 4)) {
             set_error("hs_adam_step: groups[%d]: param/grad/exp_avg/exp_avg_sq must be 4-byte aligned", i);
             return HS_EINVAL;
         }

@@ -8,7 +8,7 @@
 #include <unistd.h>
 #include <atomic>
 
-#include "hs_common.h"
+#include "hs_cloud.h"
 
 namespace hs {
 
@@ -237,20 +237,14 @@ static int check_loss_shape(int32_t planes, int32_t H, int32_t W, float lambda, 
     return HS_OK;
 }
 
-// hs_activate_args: the limits on P, and one tensor's pointers -- present (its `key` pointer given) means every pointer in
-// `need` is given, and every given pointer is 4-byte aligned
-static int check_activate_rows(const hs_activate_args* a, const char* who) {
-    if (!a) { set_error("%s: null args", who); return HS_EINVAL; }
-    if (a->P < 0 || a->P >= (1ll << 30)) { set_error("%s: P=%lld outside [0, 2^30)", who, (long long)a->P); return HS_EINVAL; }
-    return HS_OK;
-}
-
+// hs_activate_args: one tensor's pointers -- present (its `key` pointer given) means every pointer in `need` is given, and
+// every given pointer is 4-byte aligned
 static int check_activate_tensor(const char* who, const char* name, const void* key, const void* const* need, const char* const* need_names, int n) {
     if (!key) return HS_OK;
-    if ((uintptr_t)key & 3) { set_error("%s: %s must be 4-byte aligned", who, name); return HS_EINVAL; }
+    if (check_aligned(who, key, name, 4)) return HS_EINVAL;
     for (int i = 0; i < n; ++i) {
         if (!need[i]) { set_error("%s: %s is given but %s is NULL", who, name, need_names[i]); return HS_EINVAL; }
-        if ((uintptr_t)need[i] & 3) { set_error("%s: %s must be 4-byte aligned", who, need_names[i]); return HS_EINVAL; }
+        if (check_aligned(who, need[i], need_names[i], 4)) return HS_EINVAL;
     }
     return HS_OK;
 }
@@ -524,8 +518,8 @@ int hs_photometric_loss_backward(const hs_loss_args* a, void* hip_stream) {
 
 int hs_activate(const hs_activate_args* a, void* hip_stream) {
     const char* who = "hs_activate";
-    int rc = check_activate_rows(a, who);
-    if (rc) return rc;
+    if (check_args(who, a) || check_rows(who, "P", a->P)) return HS_EINVAL;
+    int rc;
     if (a->P == 0) return HS_OK;       // (no pointer is looked at)
     const void* o[] = {a->opacities}; const char* on[] = {"opacities"};
     const void* s[] = {a->scales}; const char* sn[] = {"scales"};
@@ -538,8 +532,8 @@ int hs_activate(const hs_activate_args* a, void* hip_stream) {
 
 int hs_activate_backward(const hs_activate_args* a, void* hip_stream) {
     const char* who = "hs_activate_backward";
-    int rc = check_activate_rows(a, who);
-    if (rc) return rc;
+    if (check_args(who, a) || check_rows(who, "P", a->P)) return HS_EINVAL;
+    int rc;
     if (a->g_begin < 0 || a->g_begin > a->g_end || a->g_end > a->P) {
         set_error("%s: rows [g_begin=%lld, g_end=%lld) are not inside [0, P=%lld]", who, (long long)a->g_begin, (long long)a->g_end,
                   (long long)a->P);

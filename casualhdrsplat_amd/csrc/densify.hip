@@ -25,7 +25,7 @@
 // The survivor segment is an increasing map: its reads walk the source arrays monotonically.  Nothing at or beyond row P_out
 // of a destination is written.  No atomics, no LDS in the apply; this file is compiled with -ffp-contract=off, and the order
 // of operations of a child's mean is the header's.
-#include "hs_common.h"
+#include "hs_cloud.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -40,10 +40,6 @@ constexpr int kDenThreads = 256;              // apply
 constexpr int kDenMaxGrid = 2048;             // 256 CUs x 8 workgroups; larger problems stride
 constexpr int kDenMaxMat = HS_DENSIFY_MAX_MATRICES;
 constexpr uint32_t kSrcMask = (1u << 30) - 1u;
-constexpr int64_t kDenMaxP = 1ll << 30;
-constexpr int64_t kDenMaxFloats = 1ll << 40;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct DenPlan {
     int64_t P;
@@ -194,37 +190,18 @@ __device__ __forceinline__ int64_t source_row(const DenLaunch& L, uint32_t rm) {
     return r < L.P ? r : L.P - 1;
 }
 
-// a / b and a % b of non-negative values; `small`: both below 2^32 (uniform)
-__device__ __forceinline__ void den_divmod(int64_t a, int64_t b, bool small, int64_t& q, int64_t& r) {
-    if (small) {
-        const uint32_t qq = (uint32_t)a / (uint32_t)b;
-        q = qq;
-        r = (uint32_t)a - qq * (uint32_t)b;
-    } else {
-        q = a / b;
-        r = a - q * b;
-    }
-}
-
 // component c of the mean of child k of source row `srow` (the header states this order of operations)
 __device__ __forceinline__ float child_mean(const DenLaunch& L, int64_t srow, int k, int c, float mu) {
     const float* q = L.rotations + 4 * srow;
     float w = q[0], x = q[1], y = q[2], z = q[3];
-    const float n = sqrtf(((w * w + x * x) + y * y) + z * z);
-    w = w / n; x = x / n; y = y / n; z = z / n;
+    quat_normalize(w, x, y, z);
     const float* sp = L.scales + 3 * srow;
     const float* xi = L.noise + 6 * srow + 3 * k;
     float s0 = sp[0], s1 = sp[1], s2 = sp[2];
     if (L.raw_scales) { s0 = expf(s0); s1 = expf(s1); s2 = expf(s2); }
     const float v0 = s0 * xi[0], v1 = s1 * xi[1], v2 = s2 * xi[2];
     float r0, r1, r2;
-    if (c == 0) {
-        r0 = 1.f - 2.f * (y * y + z * z); r1 = 2.f * (x * y - w * z); r2 = 2.f * (x * z + w * y);
-    } else if (c == 1) {
-        r0 = 2.f * (x * y + w * z); r1 = 1.f - 2.f * (x * x + z * z); r2 = 2.f * (y * z - w * x);
-    } else {
-        r0 = 2.f * (x * z - w * y); r1 = 2.f * (y * z + w * x); r2 = 1.f - 2.f * (x * x + y * y);
-    }
+    quat_rot_row(c, w, x, y, z, r0, r1, r2);
     return ((r0 * v0 + r1 * v1) + r2 * v2) + mu;
 }
 
@@ -243,9 +220,7 @@ __device__ __forceinline__ float den_elem(const DenMat& M, const DenLaunch& L, u
 __global__ void __launch_bounds__(kDenThreads) densify_apply_kernel(const DenLaunch L) {
     const uint32_t n_blocks = L.first_block[L.n_mat];
     for (uint32_t vb = blockIdx.x; vb < n_blocks; vb += gridDim.x) {
-        int mi = 0;
-#pragma unroll 1
-        for (int i = 1; i < L.n_mat; ++i) mi += vb >= L.first_block[i] ? 1 : 0;     // (uniform: scalar loads of the arguments)
+        HS_BLOCK_OWNER(mi, vb, L.first_block, L.n_mat);
         const DenMat& M = L.m[mi];
         const int64_t w = (int64_t)(vb - L.first_block[mi]) * kDenThreads + threadIdx.x;
         if (w >= M.n_items) continue;
@@ -253,7 +228,7 @@ __global__ void __launch_bounds__(kDenThreads) densify_apply_kernel(const DenLau
 
         if (M.mode == kMatRows4) {          // (COPY / ZERO_NEW only: MEANS and SCALES have rows of 3)
             int64_t j, q;
-            den_divmod(w, M.per_row, small, j, q);
+            divmod(w, M.per_row, small, j, q);
             const uint32_t rm = L.row_map[j];
             f4 v = {0.f, 0.f, 0.f, 0.f};
             if (!(M.role == HS_DENSIFY_ZERO_NEW && (rm >> 30) != HS_DENSIFY_KIND_SURVIVOR))
@@ -263,14 +238,14 @@ __global__ void __launch_bounds__(kDenThreads) densify_apply_kernel(const DenLau
         }
         if (M.mode == kMatScalar) {
             int64_t j, c;
-            den_divmod(w, M.S, small, j, c);
+            divmod(w, M.S, small, j, c);
             M.dst[w] = den_elem(M, L, L.row_map[j], c);
             continue;
         }
         // four consecutive floats e0 .. e0 + 3 of dst, of up to four output rows
         const int64_t e0 = 4 * w;
         int64_t j, c;
-        den_divmod(e0, M.S, small, j, c);
+        divmod(e0, M.S, small, j, c);
         uint32_t rm = L.row_map[j];          // (e0 < n_floats: row j exists)
         float v[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -296,16 +271,11 @@ __global__ void __launch_bounds__(kDenThreads) densify_apply_kernel(const DenLau
 
 // ---- host ----
 
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 int check_common(const hs_densify_args* a, const char* fn) {
-    if (!a) { set_error("%s: null args", fn); return HS_EINVAL; }
-    if (a->P < 0 || a->P >= kDenMaxP) { set_error("%s: P=%lld outside [0, 2^30)", fn, (long long)a->P); return HS_EINVAL; }
-    if (a->flags & ~(HS_DENSIFY_RAW_OPACITY | HS_DENSIFY_RAW_SCALES)) {
-        set_error("%s: flags=%d has bits other than HS_DENSIFY_RAW_OPACITY | HS_DENSIFY_RAW_SCALES", fn, a->flags);
-        return HS_EINVAL;
-    }
-    return HS_OK;
+    int rc = check_args(fn, a);
+    if (rc == HS_OK) rc = check_rows(fn, "P", a->P);
+    if (rc == HS_OK) rc = check_raw_flags(fn, a->flags);
+    return rc;
 }
 
 int check_plan_args(const hs_densify_args* a) {
@@ -317,20 +287,12 @@ int check_plan_args(const hs_densify_args* a) {
     if (a->tau_split != a->tau_split) { set_error("%s: tau_split is NaN", fn); return HS_EINVAL; }
     if (a->o_min != a->o_min) { set_error("%s: o_min is NaN", fn); return HS_EINVAL; }
     if (a->sigma_max != a->sigma_max) { set_error("%s: sigma_max is NaN (+INFINITY = off)", fn); return HS_EINVAL; }
-    if (!a->counts) { set_error("%s: null counts", fn); return HS_EINVAL; }
-    if (!aligned_to(a->counts, 4)) { set_error("%s: counts must be 4-byte aligned", fn); return HS_EINVAL; }
-    if (!aligned_to(a->counts_host, 4)) { set_error("%s: counts_host must be 4-byte aligned", fn); return HS_EINVAL; }
+    if (check_field(fn, a->counts, "counts", 4) || check_aligned(fn, a->counts_host, "counts_host", 4)) return HS_EINVAL;
     if (a->P == 0) return HS_OK;
-    const struct { const void* p; const char* name; } in[] = {
-        {a->grad_accum, "grad_accum"}, {a->denom, "denom"}, {a->max_radii, "max_radii"}, {a->opacities, "opacities"},
-        {a->scales, "scales"}, {a->row_map, "row_map"}};
-    for (const auto& f : in) {
-        if (!f.p) { set_error("%s: null %s", fn, f.name); return HS_EINVAL; }
-        if (!aligned_to(f.p, 4)) { set_error("%s: %s must be 4-byte aligned", fn, f.name); return HS_EINVAL; }
-    }
-    if (!a->workspace) { set_error("%s: null workspace", fn); return HS_EINVAL; }
-    if (!aligned_to(a->workspace, 16)) { set_error("%s: workspace must be 16-byte aligned", fn); return HS_EINVAL; }
-    return HS_OK;
+    const Field in[] = {{a->grad_accum, "grad_accum", 4}, {a->denom, "denom", 4}, {a->max_radii, "max_radii", 4},
+                        {a->opacities, "opacities", 4}, {a->scales, "scales", 4}, {a->row_map, "row_map", 4},
+                        {a->workspace, "workspace", 16}};
+    return check_fields(fn, in, 7);
 }
 
 int check_apply_args(const hs_densify_args* a) {
@@ -358,7 +320,7 @@ int check_apply_args(const hs_densify_args* a) {
             set_error("%s: matrices[%d].row_stride=%lld: the MEANS and SCALES roles take rows of 3", fn, i, (long long)M.row_stride);
             return HS_EINVAL;
         }
-        if (a->P_out > 0 && M.row_stride >= kDenMaxFloats / a->P_out) {
+        if (a->P_out > 0 && M.row_stride >= kMaxFloats / a->P_out) {
             set_error("%s: matrices[%d]: P_out * row_stride = %lld * %lld reaches 2^40", fn, i, (long long)a->P_out, (long long)M.row_stride);
             return HS_EINVAL;
         }
@@ -369,16 +331,10 @@ int check_apply_args(const hs_densify_args* a) {
         if (M.src == M.dst) { set_error("%s: matrices[%d]: dst must not be src (the gather is not in place)", fn, i); return HS_EINVAL; }
     }
     if (a->P_out == 0) return HS_OK;
-    if (!a->row_map) { set_error("%s: null row_map", fn); return HS_EINVAL; }
-    if (!aligned_to(a->row_map, 4)) { set_error("%s: row_map must be 4-byte aligned", fn); return HS_EINVAL; }
-    if (means) {
-        const struct { const void* p; const char* name; } in[] = {{a->scales, "scales"}, {a->rotations, "rotations"}, {a->noise, "noise"}};
-        for (const auto& f : in) {
-            if (!f.p) { set_error("%s: null %s (read by the HS_DENSIFY_MEANS role)", fn, f.name); return HS_EINVAL; }
-            if (!aligned_to(f.p, 4)) { set_error("%s: %s must be 4-byte aligned", fn, f.name); return HS_EINVAL; }
-        }
-    }
-    return HS_OK;
+    if (check_field(fn, a->row_map, "row_map", 4)) return HS_EINVAL;
+    if (!means) return HS_OK;
+    const Field in[] = {{a->scales, "scales", 4}, {a->rotations, "rotations", 4}, {a->noise, "noise", 4}};
+    return check_fields(fn, in, 3, " (read by the HS_DENSIFY_MEANS role)");
 }
 
 inline int64_t den_blocks(int64_t P) { return (P + kDenRows - 1) / kDenRows; }
@@ -453,10 +409,7 @@ int launch_apply(const hs_densify_args& a, hipStream_t s) {
 extern "C" {
 
 HS_API int64_t hs_densify_workspace_bytes(int64_t P) {
-    if (P < 0 || P >= hs::kDenMaxP) {
-        hs::set_error("hs_densify_workspace_bytes: P=%lld outside [0, 2^30)", (long long)P);
-        return HS_EINVAL;
-    }
+    if (hs::check_rows("hs_densify_workspace_bytes", "P", P)) return HS_EINVAL;
     return hs::align_up(P, 256) + 16 * hs::den_blocks(P);
 }
 

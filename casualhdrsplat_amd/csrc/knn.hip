@@ -28,7 +28,7 @@
 // O(P^2 / 64), still exact.
 // Kernels only, on the caller's stream: no memset, no copy, no allocation, no synchronisation, no floating-point atomics;
 // compiled with -ffp-contract=off; the same inputs give the same bits.
-#include "hs_common.h"
+#include "hs_cloud.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -41,7 +41,6 @@ constexpr int kKnnSuper = 64;                 // boxes per super-box
 constexpr int kKnnThreads = 256;
 constexpr int kKnnPartials = 256;             // most workgroups of the bounding-box reduction (one partial per thread later)
 constexpr int kKnnBits = 30;                  // Morton code: 10 bits per axis
-constexpr int64_t kKnnMaxP = 1ll << 30;
 constexpr int kKnnHdrWords = 64;              // [0] element count of the sort, [1] its fail word (+ the words it counts in)
 
 struct KnnWs {
@@ -274,19 +273,11 @@ __global__ void __launch_bounds__(kKnnBox) knn_search_kernel(const float4* __res
     }
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 int check_knn_args(const hs_knn_args* a) {
     const char* fn = "hs_knn_mean_dist_sq";
-    if (!a) { set_error("%s: null args", fn); return HS_EINVAL; }
-    if (a->P < 0 || a->P >= kKnnMaxP) { set_error("%s: P=%lld outside [0, 2^30)", fn, (long long)a->P); return HS_EINVAL; }
-    const struct { const void* p; const char* name; uintptr_t align; } in[] = {
-        {a->xyz, "xyz", 4}, {a->mean_d2, "mean_d2", 4}, {a->workspace, "workspace", 256}, {a->status, "status", 4}};
-    for (const auto& f : in) {
-        if (!f.p) { set_error("%s: null %s", fn, f.name); return HS_EINVAL; }
-        if (!aligned_to(f.p, f.align)) { set_error("%s: %s must be %d-byte aligned", fn, f.name, (int)f.align); return HS_EINVAL; }
-    }
-    return HS_OK;
+    if (check_args(fn, a) || check_rows(fn, "P", a->P)) return HS_EINVAL;
+    const Field in[] = {{a->xyz, "xyz", 4}, {a->mean_d2, "mean_d2", 4}, {a->workspace, "workspace", 256}, {a->status, "status", 4}};
+    return check_fields(fn, in, 4);
 }
 
 int launch_knn(const hs_knn_args& a, hipStream_t s) {
@@ -328,10 +319,7 @@ int launch_knn(const hs_knn_args& a, hipStream_t s) {
 extern "C" {
 
 HS_API int64_t hs_knn_workspace_bytes(int64_t P) {
-    if (P < 0 || P >= hs::kKnnMaxP) {
-        hs::set_error("hs_knn_workspace_bytes: P=%lld outside [0, 2^30)", (long long)P);
-        return HS_EINVAL;
-    }
+    if (hs::check_rows("hs_knn_workspace_bytes", "P", P)) return HS_EINVAL;
     return hs::KnnWs(P).bytes;
 }
 

@@ -23,7 +23,7 @@
 //                        their parameters were written by the launch before: the copies read what no thread here writes
 // NOISE, one kernel: one row per thread, a 16-byte load of the quaternion where the address allows, no atomics, no LDS.
 // This file is compiled with -ffp-contract=off; the order of operations of the noise is the header's.
-#include "hs_common.h"
+#include "hs_cloud.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -35,11 +35,7 @@ namespace {
 constexpr int kMcRows = 256;                  // rows per workgroup (= threads)
 constexpr int kMcScanThreads = 1024;
 constexpr int kMcMaxMat = HS_DENSIFY_MAX_MATRICES;
-constexpr int64_t kMcMaxP = 1ll << 30;
-constexpr int64_t kMcMaxFloats = 1ll << 40;
 constexpr int kMcMaxRatio = 51;
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 struct McBlock { unsigned long long sum; uint32_t dead; uint32_t pad; };   // 16 bytes per block of 256 rows
 static_assert(sizeof(McBlock) == 16, "the workspace formula counts 16 bytes per block record");
@@ -286,29 +282,23 @@ __global__ void __launch_bounds__(kMcRows) mcmc_noise_kernel(const McNoise a) {
     const int64_t i = (int64_t)blockIdx.x * kMcRows + threadIdx.x;
     if (i >= a.P) return;
     float o = a.opacities[i];
-    if (a.raw_o) o = 1.f / (1.f + expf(-o));
+    if (a.raw_o) o = sigmoid_of(o);
     const float t = (1.f - o) - 0.995f;
     const float g = 1.f / (1.f + expf(-100.f * t));
     const float gs = g * a.scaler;
     if (gs == 0.f) return;                    // the row keeps its bits (and nothing else of it is read)
-    float w, x, y, z;
-    if (a.rot16) {
-        const f4 q = *reinterpret_cast<const f4*>(a.rotations + 4 * i);
-        w = q.x; x = q.y; y = q.z; z = q.w;
-    } else {
-        const float* q = a.rotations + 4 * i;
-        w = q[0]; x = q[1]; y = q[2]; z = q[3];
-    }
-    const float n = sqrtf(((w * w + x * x) + y * y) + z * z);
-    w = w / n; x = x / n; y = y / n; z = z / n;
+    const f4 q = load_quad(a.rotations + 4 * i, a.rot16 != 0);
+    float w = q.x, x = q.y, y = q.z, z = q.w;
+    quat_normalize(w, x, y, z);
     const float* sp = a.scales + 3 * i;
     float s0 = sp[0], s1 = sp[1], s2 = sp[2];
     if (a.raw_s) { s0 = expf(s0); s1 = expf(s1); s2 = expf(s2); }
     const float* xp = a.xi + 3 * i;
     const float v0 = xp[0] * gs, v1 = xp[1] * gs, v2 = xp[2] * gs;
-    const float r00 = 1.f - 2.f * (y * y + z * z), r01 = 2.f * (x * y - w * z), r02 = 2.f * (x * z + w * y);
-    const float r10 = 2.f * (x * y + w * z), r11 = 1.f - 2.f * (x * x + z * z), r12 = 2.f * (y * z - w * x);
-    const float r20 = 2.f * (x * z - w * y), r21 = 2.f * (y * z + w * x), r22 = 1.f - 2.f * (x * x + y * y);
+    float r00, r01, r02, r10, r11, r12, r20, r21, r22;
+    quat_rot_row(0, w, x, y, z, r00, r01, r02);
+    quat_rot_row(1, w, x, y, z, r10, r11, r12);
+    quat_rot_row(2, w, x, y, z, r20, r21, r22);
     const float b0 = (s0 * s0) * ((r00 * v0 + r10 * v1) + r20 * v2);      // sigma^2 (R^T v)
     const float b1 = (s1 * s1) * ((r01 * v0 + r11 * v1) + r21 * v2);
     const float b2 = (s2 * s2) * ((r02 * v0 + r12 * v1) + r22 * v2);
@@ -321,35 +311,13 @@ __global__ void __launch_bounds__(kMcRows) mcmc_noise_kernel(const McNoise a) {
 
 // ---- host ----
 
-inline bool aligned_to(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-struct Field { const void* p; const char* name; uintptr_t align; };
-
-int check_fields(const char* fn, const Field* f, int n) {
-    for (int i = 0; i < n; ++i) {
-        if (!f[i].p) { set_error("%s: null %s", fn, f[i].name); return HS_EINVAL; }
-        if (!aligned_to(f[i].p, f[i].align)) { set_error("%s: %s must be %d-byte aligned", fn, f[i].name, (int)f[i].align); return HS_EINVAL; }
-    }
-    return HS_OK;
-}
-
-int check_flags(const char* fn, int flags) {
-    if (flags & ~(HS_DENSIFY_RAW_OPACITY | HS_DENSIFY_RAW_SCALES)) {
-        set_error("%s: flags=%d has bits other than HS_DENSIFY_RAW_OPACITY | HS_DENSIFY_RAW_SCALES", fn, flags);
-        return HS_EINVAL;
-    }
-    return HS_OK;
-}
-
 int check_mcmc_common(const hs_mcmc_args* a, const char* fn) {
-    if (!a) { set_error("%s: null args", fn); return HS_EINVAL; }
-    if (a->P < 0 || a->P >= kMcMaxP) { set_error("%s: P=%lld outside [0, 2^30)", fn, (long long)a->P); return HS_EINVAL; }
+    if (check_args(fn, a) || check_rows(fn, "P", a->P)) return HS_EINVAL;
     if (a->mode != HS_MCMC_RELOCATE && a->mode != HS_MCMC_GROW) {
         set_error("%s: mode=%d is neither HS_MCMC_RELOCATE nor HS_MCMC_GROW", fn, a->mode);
         return HS_EINVAL;
     }
-    const int rc = check_flags(fn, a->flags);
-    if (rc != HS_OK) return rc;
+    if (check_raw_flags(fn, a->flags)) return HS_EINVAL;
     if (a->mode == HS_MCMC_RELOCATE && a->n_draws != a->P) {
         set_error("%s: n_draws=%lld: a relocation has one draw slot per row (n_draws == P = %lld)", fn, (long long)a->n_draws, (long long)a->P);
         return HS_EINVAL;
@@ -366,25 +334,13 @@ int check_sample_args(const hs_mcmc_args* a) {
     const int rc = check_mcmc_common(a, fn);
     if (rc != HS_OK) return rc;
     if (a->o_min != a->o_min) { set_error("%s: o_min is NaN", fn); return HS_EINVAL; }
-    if (!a->counts) { set_error("%s: null counts", fn); return HS_EINVAL; }
-    if (!aligned_to(a->counts, 4)) { set_error("%s: counts must be 4-byte aligned", fn); return HS_EINVAL; }
-    if (!aligned_to(a->counts_host, 4)) { set_error("%s: counts_host must be 4-byte aligned", fn); return HS_EINVAL; }
-    if (!a->workspace) { set_error("%s: null workspace", fn); return HS_EINVAL; }
-    if (!aligned_to(a->workspace, 16)) { set_error("%s: workspace must be 16-byte aligned", fn); return HS_EINVAL; }
+    if (check_field(fn, a->counts, "counts", 4) || check_aligned(fn, a->counts_host, "counts_host", 4) ||
+        check_field(fn, a->workspace, "workspace", 16))
+        return HS_EINVAL;
     if (a->P == 0) return HS_OK;
-    const Field in[] = {{a->opacities, "opacities", 4}};
-    const int rf = check_fields(fn, in, 1);
-    if (rf != HS_OK) return rf;
-    if (a->n_draws > 0) {
-        const Field d[] = {{a->u, "u", 8}};
-        const int ru = check_fields(fn, d, 1);
-        if (ru != HS_OK) return ru;
-    }
-    if (a->mode == HS_MCMC_GROW) {
-        const Field d[] = {{a->row_map, "row_map", 4}};
-        const int rm = check_fields(fn, d, 1);
-        if (rm != HS_OK) return rm;
-    }
+    if (check_field(fn, a->opacities, "opacities", 4)) return HS_EINVAL;
+    if (a->n_draws > 0 && check_field(fn, a->u, "u", 8)) return HS_EINVAL;
+    if (a->mode == HS_MCMC_GROW && check_field(fn, a->row_map, "row_map", 4)) return HS_EINVAL;
     return HS_OK;
 }
 
@@ -408,7 +364,7 @@ int check_update_args(const hs_mcmc_args* a) {
             return HS_EINVAL;
         }
         if (M.row_stride < 1) { set_error("%s: matrices[%d].row_stride=%lld (need >= 1)", fn, i, (long long)M.row_stride); return HS_EINVAL; }
-        if (a->P > 0 && M.row_stride >= kMcMaxFloats / a->P) {
+        if (a->P > 0 && M.row_stride >= kMaxFloats / a->P) {
             set_error("%s: matrices[%d]: P * row_stride = %lld * %lld reaches 2^40", fn, i, (long long)a->P, (long long)M.row_stride);
             return HS_EINVAL;
         }
@@ -418,18 +374,13 @@ int check_update_args(const hs_mcmc_args* a) {
         if (M.src && M.src != M.dst) { set_error("%s: matrices[%d]: src must be NULL or dst (the update is in place)", fn, i); return HS_EINVAL; }
     }
     if (a->P == 0) return HS_OK;
-    if (!a->workspace) { set_error("%s: null workspace", fn); return HS_EINVAL; }
-    if (!aligned_to(a->workspace, 16)) { set_error("%s: workspace must be 16-byte aligned", fn); return HS_EINVAL; }
-    const Field in[] = {{a->opacities, "opacities", 4}, {a->scales, "scales", 4}};
-    return check_fields(fn, in, 2);
+    const Field in[] = {{a->workspace, "workspace", 16}, {a->opacities, "opacities", 4}, {a->scales, "scales", 4}};
+    return check_fields(fn, in, 3);
 }
 
 int check_noise_args(const hs_mcmc_noise_args* a) {
     const char* fn = "hs_mcmc_noise";
-    if (!a) { set_error("%s: null args", fn); return HS_EINVAL; }
-    if (a->P < 0 || a->P >= kMcMaxP) { set_error("%s: P=%lld outside [0, 2^30)", fn, (long long)a->P); return HS_EINVAL; }
-    const int rc = check_flags(fn, a->flags);
-    if (rc != HS_OK) return rc;
+    if (check_args(fn, a) || check_rows(fn, "P", a->P) || check_raw_flags(fn, a->flags)) return HS_EINVAL;
     if (!(a->scaler - a->scaler == 0.f)) { set_error("%s: scaler=%g is not finite", fn, (double)a->scaler); return HS_EINVAL; }
     if (a->P == 0) return HS_OK;
     const Field in[] = {{a->means3D, "means3D", 4}, {a->opacities, "opacities", 4}, {a->scales, "scales", 4},
@@ -515,14 +466,8 @@ int launch_noise(const hs_mcmc_noise_args& a, hipStream_t s) {
 extern "C" {
 
 HS_API int64_t hs_mcmc_workspace_bytes(int64_t P, int64_t n_draws) {
-    if (P < 0 || P >= hs::kMcMaxP) {
-        hs::set_error("hs_mcmc_workspace_bytes: P=%lld outside [0, 2^30)", (long long)P);
-        return HS_EINVAL;
-    }
-    if (n_draws < 0 || n_draws >= hs::kMcMaxP) {
-        hs::set_error("hs_mcmc_workspace_bytes: n_draws=%lld outside [0, 2^30)", (long long)n_draws);
-        return HS_EINVAL;
-    }
+    const char* fn = "hs_mcmc_workspace_bytes";
+    if (hs::check_rows(fn, "P", P) || hs::check_rows(fn, "n_draws", n_draws)) return HS_EINVAL;
     return hs::mc_carve(P, n_draws).bytes;
 }
 

@@ -13,7 +13,7 @@
 //                        The order is a function of P alone and every record is written before it is read: the same bits on
 //                        every run, whatever the workspace held.
 // No atomics, no memset, no copy, no synchronisation.  Compiled with -ffp-contract=off; denormals kept.
-#include "hs_common.h"
+#include "hs_cloud.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -24,7 +24,6 @@ namespace {
 
 constexpr int kRegRows = 256;                 // Gaussians per workgroup (= threads)
 constexpr int kRegSumThreads = 256;
-constexpr int64_t kRegMaxP = 1ll << 30;
 
 struct RegBlock { double o, s; };             // 16 bytes per block of 256 Gaussians
 static_assert(sizeof(RegBlock) == 16, "the workspace formula counts 16 bytes per block record");
@@ -52,7 +51,7 @@ __global__ void __launch_bounds__(kRegRows) mcmc_reg_kernel(const McReg a) {
         const float x = a.opacities[i];
         float term, mag;
         if (a.raw_o) {
-            const float o = 1.f / (1.f + expf(-x));
+            const float o = sigmoid_of(x);
             term = (1.f - o) * o;
             mag = o;
         } else {
@@ -123,16 +122,9 @@ __global__ void __launch_bounds__(kRegSumThreads) mcmc_reg_sum_kernel(const RegB
     loss[1] = (float)(lambda_s * (s / (3.0 * P)));
 }
 
-inline bool reg_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 int check_reg_args(const hs_mcmc_reg_args* a) {
     const char* fn = "hs_mcmc_regularize";
-    if (!a) { set_error("%s: null args", fn); return HS_EINVAL; }
-    if (a->P < 0 || a->P >= kRegMaxP) { set_error("%s: P=%lld outside [0, 2^30)", fn, (long long)a->P); return HS_EINVAL; }
-    if (a->flags & ~(HS_DENSIFY_RAW_OPACITY | HS_DENSIFY_RAW_SCALES)) {
-        set_error("%s: flags=%d has bits other than HS_DENSIFY_RAW_OPACITY | HS_DENSIFY_RAW_SCALES", fn, a->flags);
-        return HS_EINVAL;
-    }
+    if (check_args(fn, a) || check_rows(fn, "P", a->P) || check_raw_flags(fn, a->flags)) return HS_EINVAL;
     if (!(a->lambda_opacity >= 0.0 && a->lambda_opacity - a->lambda_opacity == 0.0)) {
         set_error("%s: lambda_opacity=%g must be finite and not negative", fn, a->lambda_opacity);
         return HS_EINVAL;
@@ -141,24 +133,17 @@ int check_reg_args(const hs_mcmc_reg_args* a) {
         set_error("%s: lambda_scale=%g must be finite and not negative", fn, a->lambda_scale);
         return HS_EINVAL;
     }
-    if (a->loss) {
-        if (!reg_aligned(a->loss, 4)) { set_error("%s: loss must be 4-byte aligned", fn); return HS_EINVAL; }
-        if (a->P > 0) {
-            if (!a->workspace) { set_error("%s: null workspace (needed with loss)", fn); return HS_EINVAL; }
-            if (!reg_aligned(a->workspace, 16)) { set_error("%s: workspace must be 16-byte aligned", fn); return HS_EINVAL; }
-        }
-    }
+    if (check_aligned(fn, a->loss, "loss", 4)) return HS_EINVAL;
     if (a->P == 0) return HS_OK;
+    if (a->loss && check_field(fn, a->workspace, "workspace", 16, " (needed with loss)")) return HS_EINVAL;
     const bool do_o = a->lambda_opacity != 0.0, do_s = a->lambda_scale != 0.0;
-    struct { const void* p; const char* name; bool needed; } f[] = {
-        {a->opacities, "opacities", do_o || a->loss != nullptr}, {a->scales, "scales", do_s || a->loss != nullptr},
-        {a->dL_dopacities, "dL_dopacities", do_o}, {a->dL_dscales, "dL_dscales", do_s}};
-    for (const auto& x : f) {
-        if (!x.needed) continue;
-        if (!x.p) { set_error("%s: null %s", fn, x.name); return HS_EINVAL; }
-        if (!reg_aligned(x.p, 4)) { set_error("%s: %s must be 4-byte aligned", fn, x.name); return HS_EINVAL; }
-    }
-    return HS_OK;
+    Field f[4];
+    int n = 0;
+    if (do_o || a->loss) f[n++] = {a->opacities, "opacities", 4};
+    if (do_s || a->loss) f[n++] = {a->scales, "scales", 4};
+    if (do_o) f[n++] = {a->dL_dopacities, "dL_dopacities", 4};
+    if (do_s) f[n++] = {a->dL_dscales, "dL_dscales", 4};
+    return check_fields(fn, f, n);
 }
 
 int launch_reg(const hs_mcmc_reg_args& a, hipStream_t s) {
@@ -195,10 +180,7 @@ int launch_reg(const hs_mcmc_reg_args& a, hipStream_t s) {
 extern "C" {
 
 HS_API int64_t hs_mcmc_reg_workspace_bytes(int64_t P) {
-    if (P < 0 || P >= hs::kRegMaxP) {
-        hs::set_error("hs_mcmc_reg_workspace_bytes: P=%lld outside [0, 2^30)", (long long)P);
-        return HS_EINVAL;
-    }
+    if (hs::check_rows("hs_mcmc_reg_workspace_bytes", "P", P)) return HS_EINVAL;
     return hs::align_up(16 * hs::reg_blocks(P), 256);
 }
 

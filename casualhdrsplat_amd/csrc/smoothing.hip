@@ -22,7 +22,7 @@
 // Minimum and maximum are exact in any order, so the decomposition changes no bit.  No atomics, no memset, no copy, no
 // synchronisation; every workspace word read was written by the first launch of the same call.  Compiled with
 // -ffp-contract=off; denormals kept.
-#include "hs_common.h"
+#include "hs_cloud.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -35,13 +35,10 @@ constexpr int kSmThreads = 256;
 constexpr int kSmMaxGrid = 2048;              // 256 CUs x 8 workgroups; larger clouds stride
 constexpr int kSmCamChunk = 64;               // cameras staged at a time
 constexpr int kSmCamFloats = 20;
-constexpr int64_t kSmMaxP = 1ll << 30;
 constexpr int64_t kSmMaxC = 1ll << 20;
 constexpr float kSmNear = 0.2f;               // the published near plane (also the rasterizer's cull)
 constexpr float kSmLo = -0.15f, kSmHi = 1.15f;
 constexpr float kSmSqrtFifth = 0.4472135901451111f;   // sqrt(0.2) rounded to fp32, bits 0x3ee4f92e
-
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 inline int64_t sm_blocks(int64_t P) {
     const int64_t b = (P + kSmThreads - 1) / kSmThreads;
@@ -168,7 +165,7 @@ struct SmRow { float o, c, oc; float sp[3], r[3], t[3]; };
 // the forward of one row; the backward calls it too, so both carry the same bits
 __device__ __forceinline__ SmRow sm_row(float x, const float l[3], float f) {
     SmRow R;
-    R.o = 1.0f / (1.0f + expf(-x));
+    R.o = sigmoid_of(x);
     const float f2 = f * f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -264,40 +261,21 @@ __global__ void __launch_bounds__(kSmThreads) smoothing_apply_kernel(const SmApp
     }
 }
 
-inline bool sm_aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-struct SmField { const void* p; const char* name; };
-
-int check_fields(const char* fn, const SmField* f, int n) {
-    for (int i = 0; i < n; ++i) {
-        if (!f[i].p) { set_error("%s: null %s", fn, f[i].name); return HS_EINVAL; }
-        if (!sm_aligned(f[i].p, 4)) { set_error("%s: %s must be 4-byte aligned", fn, f[i].name); return HS_EINVAL; }
-    }
-    return HS_OK;
-}
-
 int check_filter_args(const hs_smoothing_filter_args* a) {
     const char* fn = "hs_smoothing_filter";
-    if (!a) { set_error("%s: null args", fn); return HS_EINVAL; }
-    if (a->P < 0 || a->P >= kSmMaxP) { set_error("%s: P=%lld outside [0, 2^30)", fn, (long long)a->P); return HS_EINVAL; }
+    if (check_args(fn, a) || check_rows(fn, "P", a->P)) return HS_EINVAL;
     if (a->C < 0 || a->C >= kSmMaxC) { set_error("%s: C=%lld outside [0, 2^20)", fn, (long long)a->C); return HS_EINVAL; }
-    if (a->n_views && !sm_aligned(a->n_views, 4)) { set_error("%s: n_views must be 4-byte aligned", fn); return HS_EINVAL; }
+    if (check_aligned(fn, a->n_views, "n_views", 4)) return HS_EINVAL;
     if (a->P == 0) return HS_OK;
-    const SmField f[] = {{a->xyz, "xyz"}, {a->filter, "filter"}, {a->workspace, "workspace"}};
-    int rc = check_fields(fn, f, 3);
-    if (rc != HS_OK) return rc;
-    if (!sm_aligned(a->workspace, 256)) { set_error("%s: workspace must be 256-byte aligned", fn); return HS_EINVAL; }
-    if (a->C > 0) {
-        const SmField c[] = {{a->viewmatrices, "viewmatrices"}, {a->intrinsics, "intrinsics"}};
-        rc = check_fields(fn, c, 2);
-    }
-    return rc;
+    // (a workspace that is not even 4-byte aligned is told so first: the texts and their order are part of the contract)
+    const Field f[] = {{a->xyz, "xyz", 4}, {a->filter, "filter", 4}, {a->workspace, "workspace", 4}, {a->workspace, "workspace", 256},
+                       {a->viewmatrices, "viewmatrices", 4}, {a->intrinsics, "intrinsics", 4}};
+    return check_fields(fn, f, a->C > 0 ? 6 : 4);
 }
 
 int check_apply_args(const hs_smoothing_apply_args* a, bool backward) {
     const char* fn = backward ? "hs_smoothing_apply_backward" : "hs_smoothing_apply";
-    if (!a) { set_error("%s: null args", fn); return HS_EINVAL; }
-    if (a->P < 0 || a->P >= kSmMaxP) { set_error("%s: P=%lld outside [0, 2^30)", fn, (long long)a->P); return HS_EINVAL; }
+    if (check_args(fn, a) || check_rows(fn, "P", a->P)) return HS_EINVAL;
     if (backward) {
         if (a->g_begin < 0 || a->g_begin > a->g_end || a->g_end > a->P) {
             set_error("%s: g_begin=%lld, g_end=%lld outside 0 <= g_begin <= g_end <= P=%lld", fn, (long long)a->g_begin,
@@ -305,13 +283,13 @@ int check_apply_args(const hs_smoothing_apply_args* a, bool backward) {
             return HS_EINVAL;
         }
         if (a->g_begin == a->g_end) return HS_OK;
-        const SmField f[] = {{a->opacity_raw, "opacity_raw"}, {a->scales_raw, "scales_raw"}, {a->filter, "filter"},
-                             {a->dL_dopacities, "dL_dopacities"}, {a->dL_dscales, "dL_dscales"}};
+        const Field f[] = {{a->opacity_raw, "opacity_raw", 4}, {a->scales_raw, "scales_raw", 4}, {a->filter, "filter", 4},
+                           {a->dL_dopacities, "dL_dopacities", 4}, {a->dL_dscales, "dL_dscales", 4}};
         return check_fields(fn, f, 5);
     }
     if (a->P == 0) return HS_OK;
-    const SmField f[] = {{a->opacity_raw, "opacity_raw"}, {a->scales_raw, "scales_raw"}, {a->filter, "filter"},
-                         {a->opacities, "opacities"}, {a->scales, "scales"}};
+    const Field f[] = {{a->opacity_raw, "opacity_raw", 4}, {a->scales_raw, "scales_raw", 4}, {a->filter, "filter", 4},
+                       {a->opacities, "opacities", 4}, {a->scales, "scales", 4}};
     return check_fields(fn, f, 5);
 }
 
@@ -326,8 +304,8 @@ int launch_apply(const hs_smoothing_apply_args& a, bool backward, hipStream_t s)
     if (k.lo >= k.hi) return HS_OK;
     k.first = k.lo / 4;
     const int64_t groups = (k.hi + 3) / 4 - k.first;
-    k.vec = sm_aligned(k.x, 16) && sm_aligned(k.l, 16) && sm_aligned(k.f, 16) &&
-            (backward ? sm_aligned(k.g_o, 16) && sm_aligned(k.g_s, 16) : sm_aligned(k.o, 16) && sm_aligned(k.s, 16)) ? 1 : 0;
+    k.vec = aligned_to(k.x, 16) && aligned_to(k.l, 16) && aligned_to(k.f, 16) &&
+            (backward ? aligned_to(k.g_o, 16) && aligned_to(k.g_s, 16) : aligned_to(k.o, 16) && aligned_to(k.s, 16)) ? 1 : 0;
     const unsigned grid = (unsigned)((groups + kSmThreads - 1) / kSmThreads);      // P < 2^30: at most 2^20 workgroups
     if (backward) smoothing_apply_kernel<true><<<grid, kSmThreads, 0, s>>>(k);
     else smoothing_apply_kernel<false><<<grid, kSmThreads, 0, s>>>(k);
@@ -341,10 +319,7 @@ int launch_apply(const hs_smoothing_apply_args& a, bool backward, hipStream_t s)
 extern "C" {
 
 HS_API int64_t hs_smoothing_filter_workspace_bytes(int64_t P) {
-    if (P < 0 || P >= hs::kSmMaxP) {
-        hs::set_error("hs_smoothing_filter_workspace_bytes: P=%lld outside [0, 2^30)", (long long)P);
-        return HS_EINVAL;
-    }
+    if (hs::check_rows("hs_smoothing_filter_workspace_bytes", "P", P)) return HS_EINVAL;
     return hs::align_up(8 * hs::sm_blocks(P), 256);
 }
 

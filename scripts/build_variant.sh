@@ -1,18 +1,7 @@
 #!/bin/bash
 # Builds casualhdrsplat_amd/libhdrsplat_<name>.so = the product sources with extra -D flags on some translation units (A/B
-# and ablation experiments; the variants travel to the GPU box with the snapshot).
-# usage: bash scripts/build_variant.sh <name> <tu[,tu...]: binning|render|preprocess|api|spline> "<flags>"
+# and ablation experiments): `make variant` of casualhdrsplat_amd/csrc/Makefile under its older command line.
+# usage: bash scripts/build_variant.sh <name> <tu[,tu...]: any unit of the Makefile's OBJS, e.g. binning,render> "<flags>"
 set -e
-cd "$(dirname "$0")/../casualhdrsplat_amd/csrc"
-name=$1; tus=${2//,/ }; flags=$3
-make -s all >/dev/null
-objs=""
-for o in api preprocess binning render spline; do
-  if [[ " $tus " == *" $o "* ]]; then
-    contract=off; [ "$o" = render ] && contract=fast
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -fvisibility=hidden -std=c++17 -Wall -Wno-unused-function -ffp-contract=$contract $flags -c $o.hip -o /tmp/${o}_$name.o
-    objs="$objs /tmp/${o}_$name.o"
-  else objs="$objs $o.o"; fi
-done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o ../libhdrsplat_$name.so $objs
-echo built ../libhdrsplat_$name.so
+make -s -C "$(dirname "$0")/../casualhdrsplat_amd/csrc" variant NAME="$1" TUS="${2//,/ }" DEFS="$3"
+echo "built casualhdrsplat_amd/libhdrsplat_$1.so"
