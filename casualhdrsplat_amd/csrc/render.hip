@@ -256,9 +256,13 @@ __device__ __forceinline__ void scale_entry(float4& a, float4& b) {
 // log2(1/(255 o)).  For a centre outside the rectangle the maximum lies on one of the two edges facing it; both
 // candidates below (optimum along the nearest vertical line, optimum along the nearest horizontal line, each
 // clamped to the rectangle) are points of the rectangle and one of them is the constrained optimum, so the test is
-// exact up to rounding.  The threshold carries an absolute margin of 0.05 in log2 units (+1e-4 relative), orders
-// of magnitude above the fp32 evaluation error of the inner loops for variance ratios up to ~1e5, so culling
-// never changes a result.
+// exact up to rounding.  The threshold carries an absolute margin of 0.05 in log2 units (+1e-4 relative).  What it has
+// to cover is the fp32 evaluation error of p1 / p2 below and of the inner loops, which grows with the footprint's
+// conditioning: about 6 * 2^-24 * log2(e) * M, M = the sum of the ABSOLUTE values of the quadratic's three terms at the
+// point evaluated -- 1e-6 for a well-rounded footprint (M ~ 10), 0.02 at M = 4e4, the largest any
+// contributing (pixel, entry) reaches in the needle and disc scenes of tests/test_anisotropy_gpu.py (projected variance
+// ratios up to 2.4e5, radii up to 1100 px), where no contributor is culled.  The margin is used up at M ~ 1e5; no
+// claim is made beyond the scenes tested.
 template <int WIDTH>   // rectangle [sx, sx + WIDTH - 1] x [sy, sy + 7]: 16 = a half tile, 8 = the 8 x 8 block of a lane group
 __device__ __forceinline__ bool block_may_touch(const float4 a, const float4 b, float sx, float sy) {
     const float A2 = a.z, B2 = a.w, C2 = b.x, o = b.y;

@@ -272,3 +272,29 @@ def extreme_scene(name: str, seed: int = 0) -> Scene:
     else:
         raise ValueError(name)
     return sc
+
+
+def anisotropic_scene(kind: str, ratio: float, fraction: float, seed: int = 0, P: int = 3000, W: int = 240, H: int = 160,
+                      sh_degree: int = 1) -> Scene:
+    """make_scene's cloud (its draws untouched: axis ratios below e) with a random `fraction` of the Gaussians reshaped into
+    what trained clouds are largely made of (tests: test_anisotropy*.py): the geometric mean of the three scales kept, their
+    ratios redrawn with r log-uniform in [1, ratio] --
+      needle   (r^2/3, r^-1/3, r^-1/3)   one long axis, r times the other two
+      disc     (r^1/3, r^1/3, r^-2/3)    two long axes, r times the thin one
+    -- the rotations stay make_scene's random quaternions, so footprints point every way and discs are seen at every tilt."""
+    if kind not in ("needle", "disc"):
+        raise ValueError(kind)
+    if not (ratio >= 1.0 and 0.0 <= fraction <= 1.0):
+        raise ValueError((ratio, fraction))
+    sc = make_scene(P, W, H, sh_degree, seed=seed)
+    g = torch.Generator().manual_seed(9_000_011 + seed)
+    chosen = torch.rand(P, generator=g, dtype=torch.float64) < fraction
+    r = torch.exp(math.log(ratio) * torch.rand(P, generator=g, dtype=torch.float64))
+    s = sc.scales.double()
+    gm = s.prod(dim=1) ** (1.0 / 3.0)
+    if kind == "needle":
+        shape = torch.stack([r ** (2.0 / 3.0), r ** (-1.0 / 3.0), r ** (-1.0 / 3.0)], dim=1)
+    else:
+        shape = torch.stack([r ** (1.0 / 3.0), r ** (1.0 / 3.0), r ** (-2.0 / 3.0)], dim=1)
+    sc.scales = torch.where(chosen[:, None], gm[:, None] * shape, s).float()
+    return sc

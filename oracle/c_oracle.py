@@ -52,6 +52,9 @@ def lib():
         _lib.hso_scan.restype = C.c_int64
         _lib.hso_threshold_risk.restype = C.c_int64
         _lib.hso_pixel_reach.restype = C.c_int64
+        _lib.hso_threshold_risk_cond.restype = C.c_int64
+        _lib.hso_pixel_reach_cond.restype = C.c_int64
+        _lib.hso_cond_k.restype = C.c_double
     return _lib
 
 
@@ -147,16 +150,54 @@ def forward(cam: Camera, means3D, opacities, shs=None, colors_precomp=None, scal
     return o
 
 
-def threshold_risk(cam: Camera, fwd: dict, guard_alpha: float = 2e-5, guard_T: float = 1e-4) -> dict:
+# The conditioning constant k: two correct fp32 evaluations of the power of one (pixel, entry) -- this oracle's and the
+# render kernel's pre-scaled base-2 form -- differ by at most k 2^-24 M, M = 0.5|A|dx^2 + 0.5|C|dy^2 + |B||dx dy|.  Derived by
+# counting roundings (4 + 5.22, rounded up), not fitted: the count is written out in hs_oracle.c at HSO_COND_K, which
+# this must equal (tests/test_anisotropy.py).
+K_COND = 10.0
+U24 = 2.0 ** -24
+
+
+def _check_k(k):
+    k = float(k)
+    if not (np.isfinite(k) and k > 0.0):
+        raise ValueError(f"conditioned: k must be a finite number > 0, got {k!r}")
+    return k
+
+
+def threshold_risk(cam: Camera, fwd: dict, guard_alpha: float = 2e-5, guard_T: float = 1e-4, conditioned=None) -> dict:
     """Guard band of the frame `fwd` (forward()'s dict) around the three piecewise-constant decisions of the
     compositing loop (hso_threshold_risk): pixels / Gaussians on which another fp32 implementation may legitimately
-    decide differently, and the smallest margins seen.  guard_alpha is relative to 1/255, guard_T relative to 1e-4."""
+    decide differently, and the smallest margins seen.  guard_alpha is relative to 1/255, guard_T relative to 1e-4.
+
+    conditioned=k (None: the fixed band above, unchanged): hso_threshold_risk_cond -- every test widened by k 2^-24 M of its
+    own (pixel, entry) -- and, next to the keys above, what identical decisions still leave between two implementations:
+    `T_tol` [H,W] (relative difference of final_T) and `color_tol` [3,H,W] (absolute difference of the colour), both
+    k 2^-24 times the unit sums `T_units` / `color_units`; `max_M` (largest M of a contributing entry), `power_c`
+    (largest |power - float64 power| / (2^-24 M) over every (pixel, entry) walked) and `n_pairs`."""
     L = lib()
     P = fwd["radii"].shape[0]
     c = cam.cstruct(P, 0)
     pix = np.zeros((cam.H, cam.W), np.uint8)
     gs = np.zeros(P, np.uint8)
     mm = np.zeros(3, np.float64)
+    if conditioned is not None:
+        k = _check_k(conditioned)
+        if not (guard_alpha >= 0 and guard_T >= 0):
+            raise ValueError("guards must be >= 0")
+        tu = np.zeros((cam.H, cam.W), np.float32)
+        cu = np.zeros((3, cam.H, cam.W), np.float32)
+        stats = np.zeros(4, np.float64)
+        n = int(L.hso_threshold_risk_cond(C.byref(c), _p(fwd["ranges"]), _p(fwd["point_list"]), _p(fwd["xy"]),
+                                          _p(fwd["conic_opacity"]), _p(_f32(fwd["rgb"])), C.c_float(guard_alpha),
+                                          C.c_float(guard_T), C.c_double(k), _p(pix), _p(gs), _p(mm), _p(tu), _p(cu), _p(stats)))
+        if n < 0:
+            raise ValueError("hso_threshold_risk_cond refused its arguments")
+        return dict(n_risky_pixels=n, pix_risk=pix.astype(bool), gauss_risk=gs.astype(bool),
+                    min_margin_alpha=float(mm[0]), min_margin_T=float(mm[1]), min_abs_power=float(mm[2]), k=k,
+                    T_units=tu, color_units=cu, T_tol=k * U24 * tu.astype(np.float64),
+                    color_tol=k * U24 * cu.astype(np.float64), max_M=float(stats[0]), power_c=float(stats[1]),
+                    max_T_units=float(stats[2]), n_pairs=int(stats[3]))
     n = int(L.hso_threshold_risk(C.byref(c), _p(fwd["ranges"]), _p(fwd["point_list"]), _p(fwd["xy"]),
                                  _p(fwd["conic_opacity"]), C.c_float(guard_alpha), C.c_float(guard_T), _p(pix), _p(gs),
                                  _p(mm)))
@@ -164,22 +205,34 @@ def threshold_risk(cam: Camera, fwd: dict, guard_alpha: float = 2e-5, guard_T: f
                 min_margin_alpha=float(mm[0]), min_margin_T=float(mm[1]), min_abs_power=float(mm[2]))
 
 
-def pixel_reach(cam: Camera, fwd: dict, pix_mask, whole_list: bool = False, guard_alpha: float = 1e-5) -> np.ndarray:
+def pixel_reach(cam: Camera, fwd: dict, pix_mask, whole_list: bool = False, guard_alpha: float = 1e-5,
+                conditioned=None) -> np.ndarray:
     """bool [P]: the Gaussians that contribute to the pixels selected by `pix_mask` [H,W] (hso_pixel_reach).
     whole_list: every entry of those pixels' tile lists that ANY fp32 implementation may have blended (alpha within
-    guard_alpha of the 1/255 threshold or above, no early termination) instead of this oracle's own contributors."""
+    guard_alpha of the 1/255 threshold or above, no early termination) instead of this oracle's own contributors.
+    conditioned=k: the whole_list alpha test widened by k 2^-24 M per entry (hso_pixel_reach_cond)."""
     L = lib()
     P = fwd["radii"].shape[0]
     c = cam.cstruct(P, 0)
     m = np.ascontiguousarray(np.asarray(pix_mask).astype(np.uint8))
+    if m.shape != (cam.H, cam.W):
+        raise ValueError(f"pix_mask must be [H,W] = {(cam.H, cam.W)}, got {m.shape}")
     gs = np.zeros(P, np.uint8)
+    if conditioned is not None:
+        rc = L.hso_pixel_reach_cond(C.byref(c), _p(fwd["ranges"]), _p(fwd["point_list"]), _p(fwd["xy"]),
+                                    _p(fwd["conic_opacity"]), _p(m), _p(gs), C.c_int(int(whole_list)), C.c_float(guard_alpha),
+                                    C.c_double(_check_k(conditioned)))
+        if rc < 0:
+            raise ValueError("hso_pixel_reach_cond refused its arguments")
+        return gs.astype(bool)
     L.hso_pixel_reach(C.byref(c), _p(fwd["ranges"]), _p(fwd["point_list"]), _p(fwd["xy"]), _p(fwd["conic_opacity"]), _p(m), _p(gs),
                       C.c_int(int(whole_list)), C.c_float(guard_alpha))
     return gs.astype(bool)
 
 
 def backward(cam: Camera, fwd: dict, dL_dcolor_img, means3D, shs=None, colors_precomp=None,
-             scales=None, rotations=None, cov3D_precomp=None, dL_dinvdepth_img=None, bounds: bool = False) -> dict:
+             scales=None, rotations=None, cov3D_precomp=None, dL_dinvdepth_img=None, bounds: bool = False,
+             conditioned: bool = False) -> dict:
     """Runs a10..a12 given forward()'s intermediates and dL/d(out_color) [3,H,W] (+ optional dL/d(invdepth) [H,W]).
 
     bounds=True adds, next to every gradient tensor `dL_dX`, `abs_dL_dX` of the same shape = sum |terms| of that
@@ -187,7 +240,12 @@ def backward(cam: Camera, fwd: dict, dL_dcolor_img, means3D, shs=None, colors_pr
     pixels of the magnitude of what it added (hso_render_bwd, abs_terms); a11/a12 are linear in those sums, so the
     magnitudes are carried through them by hso_preprocess_bwd_abs -- the same chain with every coefficient's absolute
     value and every difference turned into a sum (a net Jacobian entry that is small by cancellation still carries the
-    rounding of the intermediates it cancelled from)."""
+    rounding of the intermediates it cancelled from).
+
+    conditioned=True (with bounds): a second set `cond_dL_dX` -- the same magnitudes weighted by M_i + T_units(pixel)
+    instead of 4 + steps (hso_render_bwd_cond), carried through a11 / a12 the same way; the gradients and abs_* do not change."""
+    if conditioned and not bounds:
+        raise ValueError("conditioned=True needs bounds=True")
     L = lib()
     means3D = _f32(means3D)
     P = means3D.shape[0]
@@ -203,11 +261,16 @@ def backward(cam: Camera, fwd: dict, dL_dcolor_img, means3D, shs=None, colors_pr
     )
     gd = None if dL_dinvdepth_img is None else _f32(dL_dinvdepth_img).reshape(cam.H, cam.W)
     o["dL_dinvdepth"] = None if gd is None else np.zeros(P, np.float32)
-    rc = L.hso_render_bwd(C.byref(c), _p(fwd["ranges"]), _p(fwd["point_list"]), _p(fwd["xy"]),
-                          _p(fwd["conic_opacity"]), _p(fwd["rgb"]), _p(fwd["final_T"]), _p(fwd["n_contrib"]),
-                          _p(g), _p(o["dL_dmean2D"]), _p(o["dL_dconic"]), _p(o["dL_dopacity"]),
-                          _p(o["dL_dcolor"]), _p(o["abs_terms"]),
-                          _p(fwd["depths"]) if gd is not None else None, _p(gd), _p(o["dL_dinvdepth"]))
+    rb_args = (C.byref(c), _p(fwd["ranges"]), _p(fwd["point_list"]), _p(fwd["xy"]),
+               _p(fwd["conic_opacity"]), _p(fwd["rgb"]), _p(fwd["final_T"]), _p(fwd["n_contrib"]),
+               _p(g), _p(o["dL_dmean2D"]), _p(o["dL_dconic"]), _p(o["dL_dopacity"]),
+               _p(o["dL_dcolor"]), _p(o["abs_terms"]),
+               _p(fwd["depths"]) if gd is not None else None, _p(gd), _p(o["dL_dinvdepth"]))
+    if conditioned:
+        o["cond_terms"] = np.zeros((P, 10), np.float32)
+        rc = L.hso_render_bwd_cond(*rb_args, _p(o["cond_terms"]))
+    else:
+        rc = L.hso_render_bwd(*rb_args)
     assert rc == 0
     o["dL_dmeans3D"] = np.zeros((P, 3), np.float32)
     o["dL_dshs"] = np.zeros((P, M, 3), np.float32) if shs is not None else None
@@ -224,9 +287,11 @@ def backward(cam: Camera, fwd: dict, dL_dcolor_img, means3D, shs=None, colors_pr
                               _p(_f32(fwd["opacities_in"])), _p(o["dL_dopacity"]), _p(o["dL_dinvdepth"]))
     assert rc == 0
     o["dL_dmeans2D"] = np.concatenate([o["dL_dmean2D"], np.zeros((P, 1), np.float32)], axis=1)
-    if bounds:
-        A = o["abs_terms"]
-        o["n_terms"] = A[:, 10].astype(np.int64)
+    for pre, A in (("abs_", o["abs_terms"] if bounds else None), ("cond_", o.get("cond_terms"))):
+        if A is None:
+            continue
+        if pre == "abs_":
+            o["n_terms"] = A[:, 10].astype(np.int64)
         outs = ["dL_dmeans3D", "dL_dshs", "dL_dcolors_precomp", "dL_dscales", "dL_drots", "dL_dcov3D"]
         t = {q: (None if o[q] is None else np.zeros(o[q].shape, np.float32)) for q in outs}
         m2, con, col = (np.ascontiguousarray(A[:, 0:2]), np.ascontiguousarray(A[:, 2:5]), np.ascontiguousarray(A[:, 6:9]))
@@ -238,9 +303,9 @@ def backward(cam: Camera, fwd: dict, dL_dcolor_img, means3D, shs=None, colors_pr
                                       _p(_f32(fwd["opacities_in"])), _p(op), _p(invd if gd is not None else None))
         assert rc == 0
         for q in outs:
-            o["abs_" + q] = t[q]
-        o["abs_dL_dopacity"] = op        # (antialiasing scaled it in place; else it passed through)
-        o["abs_dL_dmeans2D"] = np.concatenate([A[:, :2], np.zeros((P, 1), np.float32)], axis=1)
+            o[pre + q] = t[q]
+        o[pre + "dL_dopacity"] = op        # (antialiasing scaled it in place; else it passed through)
+        o[pre + "dL_dmeans2D"] = np.concatenate([A[:, :2], np.zeros((P, 1), np.float32)], axis=1)
     return o
 
 

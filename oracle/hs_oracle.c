@@ -416,6 +416,45 @@ int hso_render_fwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
 }
 
 /* ------------------------------------------------------------------------------------------
+ * Conditioning of the power (opt-in; every entry point above and below keeps its results bit for bit when it is off).
+ *
+ * power = -0.5 (A dx^2 + C dy^2) - B dx dy is a difference of terms whose absolute sum is
+ *       M = 0.5 |A| dx^2 + 0.5 |C| dy^2 + |B| |dx dy| .
+ * For a well-rounded footprint M ~ |power|; for a needle or a disc seen edge-on (variance ratio rho) M reaches rho |power|,
+ * and two correct fp32 evaluations of the same conic bits differ in `power` -- hence RELATIVELY in alpha = o exp(power) --
+ * by a multiple of u M, u = 2^-24 (one rounding to nearest).  The multiple HSO_COND_K is derived, not fitted, by counting
+ * the roundings each term goes through (first order in u; dx, dy are the same bits on both sides: one subtraction of
+ * the same operands):
+ *   this file:   -0.5f * ((A*dx)*dx + (C*dy)*dy) - (B*dx)*dy
+ *       A term: A*dx, *dx, the inner sum, the final difference          4   (the product with -0.5 is exact)
+ *       C term: C*dy, *dy, the inner sum, the final difference          4
+ *       B term: B*dx, *dy, the final difference                         3          -> at most 4 u M
+ *   render.hip:  A2 = A*(-0.5 L), B2 = B*(-L), C2 = C*(-0.5 L), L = fl(log2 e) (scale_entry), then
+ *                log2 G = dy*(C2*dy + B2*dx) + (A2*dx)*dx, taken back to base e by 1 / log2 e
+ *       C term: C2, C2*dy, the inner sum, dy*(..), the final sum        5
+ *       B term: B2, B2*dx, the inner sum, dy*(..), the final sum        5
+ *       A term: A2, A2*dx, *dx, the final sum                           4
+ *       L itself is log2 e rounded once (0.22 u as it happens), on every term              -> at most 5.22 u M
+ *     (the compiler contracts some of these into fused multiply-adds: fewer roundings, never more)
+ * Together 9.22 u M, rounded up: HSO_COND_K = 10.  Each evaluation alone stays within about half of it of the exact
+ * value (tests/test_anisotropy.py holds both to (k/2) u M against float64 on the same conic bits).  What the two
+ * exponentials add (expf against exp2 of the hardware, a few u relative) is independent of M and stays in the fixed
+ * guard_alpha / guard_T, as before.
+ * ------------------------------------------------------------------------------------------ */
+#define HSO_COND_K 10.0
+#define HSO_U24 5.9604644775390625e-08 /* 2^-24 */
+double hso_cond_k(void) { return HSO_COND_K; }
+
+static inline double power_mag(const float* co, float dx, float dy) {
+    const double x = (double)dx, y = (double)dy;
+    return 0.5 * fabs((double)co[0]) * x * x + 0.5 * fabs((double)co[2]) * y * y + fabs((double)co[1]) * fabs(x * y);
+}
+static inline double power_f64(const float* co, float dx, float dy) {
+    const double x = (double)dx, y = (double)dy;
+    return -0.5 * ((double)co[0] * x * x + (double)co[2] * y * y) - (double)co[1] * x * y;
+}
+
+/* ------------------------------------------------------------------------------------------
  * Threshold guard band of a rendered frame (test infrastructure for SURVEY.md 7.4-3).  The forward takes three
  * piecewise-constant decisions per (pixel, entry): `power > 0`, `alpha < 1/255` and `T (1 - alpha) < 1e-4`.  Any other
  * fp32 implementation (a GPU's exp2-based falloff, a different multiplication order of T) may land on the other side
@@ -428,9 +467,12 @@ int hso_render_fwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
  * Fixtures are reject-sampled until no pixel is at risk; comparators of larger scenes require every difference in the
  * decisions to sit on a pixel at risk and apply the strict gradient tolerance to the Gaussians that are not.
  * ------------------------------------------------------------------------------------------ */
-int64_t hso_threshold_risk(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
+/* The walk behind hso_threshold_risk (k = 0, no extra output: exactly the function documented above) and
+ * hso_threshold_risk_cond (k > 0: every test widened by err = k 2^-24 M of its own (pixel, entry), see there). */
+static int64_t threshold_risk_impl(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
                            const float* conic_opacity, float guard_alpha, float guard_T, uint8_t* pix_risk,
-                           uint8_t* gauss_risk, double* min_margin) {
+                           uint8_t* gauss_risk, double* min_margin, const double kc, const float* rgb,
+                           float* T_units, float* color_units, double* stats) {
     const int W = c->W, H = c->H;
     const int gx = (W + HSO_TILE - 1) / HSO_TILE;
     int64_t n_risky = 0;
@@ -444,27 +486,56 @@ int64_t hso_threshold_risk(const hso_camera* c, const uint32_t* ranges, const ui
             float T = 1.0f;
             int risky = 0, risky_T = 0;
             uint32_t k_end = end;
+            double Uacc = 0.0;                    /* sum alpha_j / (1 - alpha_j) M_j over the contributors so far */
+            double colU[3] = {0.0, 0.0, 0.0};     /* sum |c_j| alpha_j T_j (M_j + U_j) */
             for (uint32_t k = beg; k < end; ++k) {
                 uint32_t id = point_list[k];
                 float dx = xy[2 * id] - pxf, dy = xy[2 * id + 1] - pyf;
                 const float* co = conic_opacity + 4 * id;
                 float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
                 double ap = fabs((double)power);
+                double Mq = 0.0, err = 0.0;
+                if (kc > 0.0) {
+                    Mq = power_mag(co, dx, dy);
+                    err = kc * HSO_U24 * Mq;
+                    if (stats) {
+                        stats[3] += 1.0;
+                        if (Mq > 0.0) {
+                            const double q = fabs((double)power - power_f64(co, dx, dy)) / (HSO_U24 * Mq);
+                            if (q > stats[1]) stats[1] = q;
+                        }
+                    }
+                }
                 if (ap > 0.0 && ap < min_margin[2]) min_margin[2] = ap;
-                if (ap > 0.0 && ap < 1e-6) risky = 1;
+                if (ap > 0.0 && ap < (err > 1e-6 ? err : 1e-6)) risky = 1;
                 if (power > 0.0f) continue;
                 float alpha = fminf_(0.99f, co[3] * expf(power));
                 double ma = fabs((double)alpha * 255.0 - 1.0);
                 if (ma < min_margin[0]) min_margin[0] = ma;
-                if (ma < guard_alpha) risky = 1;
+                if (ma < guard_alpha + err) risky = 1;
                 if (alpha < 1.0f / 255.0f) continue;
                 float test_T = T * (1.f - alpha);
                 double mt = fabs((double)test_T * 1e4 - 1.0);
                 if (mt < min_margin[1]) min_margin[1] = mt;
-                if (mt < guard_T) risky = risky_T = 1;
+                /* test_T carries the factors (1 - alpha_j) of the contributors in front AND this entry's own */
+                const double Unext = Uacc + (double)alpha / (1.0 - (double)alpha) * Mq;
+                if (mt < guard_T + kc * HSO_U24 * Unext) risky = risky_T = 1;
                 if (test_T < 0.0001f) { k_end = k + 1; break; }
+                if (kc > 0.0) {
+                    if (stats && Mq > stats[0]) stats[0] = Mq;
+                    if (color_units)
+                        for (int ch = 0; ch < 3; ++ch)
+                            colU[ch] += fabs((double)rgb[3 * id + ch]) * (double)alpha * (double)T * (Mq + Uacc);
+                    Uacc = Unext;
+                }
                 T = test_T;
             }
+            if (T_units) T_units[(size_t)py * W + px] = (float)Uacc;
+            if (color_units)
+                for (int ch = 0; ch < 3; ++ch)
+                    color_units[(size_t)ch * H * W + (size_t)py * W + px] =
+                        (float)(colU[ch] + (double)T * fabs((double)c->bg[ch]) * Uacc);
+            if (stats && Uacc > stats[2]) stats[2] = Uacc;
             pix_risk[(size_t)py * W + px] = (uint8_t)risky;
             if (risky) {
                 ++n_risky;
@@ -478,14 +549,49 @@ int64_t hso_threshold_risk(const hso_camera* c, const uint32_t* ranges, const ui
                         float dx = xy[2 * id] - pxf, dy = xy[2 * id + 1] - pyf;
                         const float* co = conic_opacity + 4 * id;
                         float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
-                        if (power > 1e-6f) continue;
+                        const double err = kc > 0.0 ? kc * HSO_U24 * power_mag(co, dx, dy) : 0.0;
+                        if (kc > 0.0 ? (double)power > (err > 1e-6 ? err : 1e-6) : power > 1e-6f) continue;
                         float alpha = fminf_(0.99f, co[3] * expf(power));
-                        if ((double)alpha * 255.0 >= 1.0 - guard_alpha) gauss_risk[id] = 1;
+                        if ((double)alpha * 255.0 >= 1.0 - guard_alpha - err) gauss_risk[id] = 1;
                     }
                 }
             }
         }
     return n_risky;
+}
+
+int64_t hso_threshold_risk(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
+                           const float* conic_opacity, float guard_alpha, float guard_T, uint8_t* pix_risk,
+                           uint8_t* gauss_risk, double* min_margin) {
+    return threshold_risk_impl(c, ranges, point_list, xy, conic_opacity, guard_alpha, guard_T, pix_risk, gauss_risk,
+                               min_margin, 0.0, NULL, NULL, NULL, NULL);
+}
+
+/* The conditioned guard band: hso_threshold_risk with err = k 2^-24 M of each (pixel, entry) (see HSO_COND_K) added to
+ * every test --
+ *   `power > 0`        at risk when 0 < |power| < max(1e-6, err),
+ *   `alpha < 1/255`    at risk when |255 alpha - 1| < guard_alpha + err,
+ *   `test_T < 1e-4`    at risk when |1e4 test_T - 1| < guard_T + E,  E = k 2^-24 sum alpha_j / (1 - alpha_j) M_j over the
+ *                      contributors in front and the entry itself (the factors test_T is made of),
+ * gauss_risk with the same widened alpha test -- and, per pixel, what identical decisions still leave between two
+ * implementations, in units of k 2^-24 (the caller multiplies):
+ *   T_units[H*W]       sum_j alpha_j / (1 - alpha_j) M_j over the pixel's contributors: the relative difference of final_T,
+ *   color_units[3*H*W] sum_j |c_j| alpha_j T_j (M_j + U_j) + T |bg| U, U_j the same sum over the contributors in front of j:
+ *                      the absolute difference of the colour (rgb: [P,3], the colours the render blends).
+ * stats[4] (may be NULL): the largest M of a contributing entry; the largest |power - float64 power| / (2^-24 M) over every
+ * (pixel, entry), float64 from the same fp32 conic and centre bits -- the instrument's own check of the 4 u M above --;
+ * the largest T_units; the number of (pixel, entry) pairs walked.
+ * Returns the number of pixels at risk, or -1 for a bad argument (k not finite or <= 0, a guard < 0, a missing array). */
+int64_t hso_threshold_risk_cond(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
+                                const float* conic_opacity, const float* rgb, float guard_alpha, float guard_T, double k,
+                                uint8_t* pix_risk, uint8_t* gauss_risk, double* min_margin, float* T_units,
+                                float* color_units, double* stats) {
+    if (!c || !ranges || !point_list || !xy || !conic_opacity || !pix_risk || !min_margin) return -1;
+    if (!(k > 0.0) || !(k < 1e6) || !(guard_alpha >= 0.f) || !(guard_T >= 0.f)) return -1;
+    if (color_units && !rgb) return -1;
+    if (stats) stats[0] = stats[1] = stats[2] = stats[3] = 0.0;
+    return threshold_risk_impl(c, ranges, point_list, xy, conic_opacity, guard_alpha, guard_T, pix_risk, gauss_risk,
+                               min_margin, k, rgb, T_units, color_units, stats);
 }
 
 /* Test aid: the Gaussians that contribute to the pixels of `pix_mask` (u8 [H,W], non-zero = selected) -- the rows of
@@ -495,9 +601,9 @@ int64_t hso_threshold_risk(const hso_camera* c, const uint32_t* ranges, const ui
  * decision -- alpha within `guard_alpha` (relative) of 1/255 or above, no termination -- i.e. the rows another fp32
  * implementation that decided differently on this pixel may have touched.  Marks gauss_out[id] = 1; returns the number
  * of selected pixels. */
-int64_t hso_pixel_reach(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
+static int64_t pixel_reach_impl(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
                         const float* conic_opacity, const uint8_t* pix_mask, uint8_t* gauss_out, int whole_list,
-                        float guard_alpha) {
+                        float guard_alpha, const double kc) {
     const int W = c->W, H = c->H;
     const int gx = (W + HSO_TILE - 1) / HSO_TILE;
     int64_t n = 0;
@@ -515,9 +621,10 @@ int64_t hso_pixel_reach(const hso_camera* c, const uint32_t* ranges, const uint3
                 const float* co = conic_opacity + 4 * id;
                 float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
                 if (whole_list) {
-                    if (power > 1e-6f) continue;
+                    const double err = kc > 0.0 ? kc * HSO_U24 * power_mag(co, dx, dy) : 0.0;
+                    if (kc > 0.0 ? (double)power > (err > 1e-6 ? err : 1e-6) : power > 1e-6f) continue;
                     float alpha = fminf_(0.99f, co[3] * expf(power));
-                    if ((double)alpha * 255.0 >= 1.0 - guard_alpha) gauss_out[id] = 1;
+                    if ((double)alpha * 255.0 >= 1.0 - guard_alpha - err) gauss_out[id] = 1;
                     continue;
                 }
                 if (power > 0.0f) continue;
@@ -530,6 +637,22 @@ int64_t hso_pixel_reach(const hso_camera* c, const uint32_t* ranges, const uint3
             }
         }
     return n;
+}
+
+int64_t hso_pixel_reach(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
+                        const float* conic_opacity, const uint8_t* pix_mask, uint8_t* gauss_out, int whole_list,
+                        float guard_alpha) {
+    return pixel_reach_impl(c, ranges, point_list, xy, conic_opacity, pix_mask, gauss_out, whole_list, guard_alpha, 0.0);
+}
+
+/* hso_pixel_reach whose whole_list form takes the alpha test widened by err = k 2^-24 M, as hso_threshold_risk_cond does
+ * (whole_list = 0 does not depend on k).  -1 for a bad argument. */
+int64_t hso_pixel_reach_cond(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list, const float* xy,
+                             const float* conic_opacity, const uint8_t* pix_mask, uint8_t* gauss_out, int whole_list,
+                             float guard_alpha, double k) {
+    if (!c || !ranges || !point_list || !xy || !conic_opacity || !pix_mask || !gauss_out) return -1;
+    if (!(k > 0.0) || !(k < 1e6) || !(guard_alpha >= 0.f)) return -1;
+    return pixel_reach_impl(c, ranges, point_list, xy, conic_opacity, pix_mask, gauss_out, whole_list, guard_alpha, k);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -547,12 +670,12 @@ int64_t hso_pixel_reach(const hso_camera* c, const uint32_t* ranges, const uint3
  * column 10 the number of terms n.  Tests bound |other implementation - this one| per element by
  * 1e-4 |ref| + c 2^-24 sum w |term| (tests/helpers.py, assert_grads_bounded).
  * ------------------------------------------------------------------------------------------ */
-int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list,
+static int render_bwd_impl(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list,
                    const float* xy, const float* conic_opacity, const float* rgb,
                    const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                    float* abs_terms,
-                   const float* depths, const float* dL_dinvdepth_pix, float* dL_dinvdepth) {
+                   const float* depths, const float* dL_dinvdepth_pix, float* dL_dinvdepth, float* cond_terms) {
     /* depths, dL_dinvdepth_pix [H*W], dL_dinvdepth [P] (all or none): the inverse-depth image is a fourth blended
      * channel without a background term; dL_dinvdepth receives sum_pix alpha T dL/dD(pix) per Gaussian */
     const int W = c->W, H = c->H, P = c->P;
@@ -561,6 +684,9 @@ int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
     if (!acc) return -1;
     double* aab = abs_terms ? (double*)calloc((size_t)P * 11, sizeof(double)) : NULL;
     if (abs_terms && !aab) { free(acc); return -1; }
+    /* cond_terms [P, 10] (hso_render_bwd_cond): the magnitudes of abs_terms' ten sums weighted by M_i + U(pixel) instead */
+    double* aac = cond_terms ? (double*)calloc((size_t)P * 10, sizeof(double)) : NULL;
+    if (cond_terms && !aac) { free(acc); free(aab); return -1; }
     const float ddelx_dx = 0.5f * (float)W, ddely_dy = 0.5f * (float)H;
     for (int py = 0; py < H; ++py)
         for (int px = 0; px < W; ++px) {
@@ -579,6 +705,18 @@ int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
             float last_alpha = 0.f;
             float pxf = (float)px, pyf = (float)py;
             double wdepth = 4.0;   /* abs_terms weight: 4 + the T / (1 - alpha) steps behind this contributor (see below) */
+            double Upix = 0.0;     /* cond_terms: sum alpha_j / (1 - alpha_j) M_j over this pixel's contributors */
+            if (aac)
+                for (uint32_t kk = 0; kk < last; ++kk) {
+                    uint32_t id = point_list[beg + kk];
+                    float dx = xy[2 * id] - pxf, dy = xy[2 * id + 1] - pyf;
+                    const float* co = conic_opacity + 4 * id;
+                    float power = -0.5f * (co[0] * dx * dx + co[2] * dy * dy) - co[1] * dx * dy;
+                    if (power > 0.0f) continue;
+                    float alpha = fminf_(0.99f, co[3] * expf(power));
+                    if (alpha < 1.0f / 255.0f) continue;
+                    Upix += (double)alpha / (1.0 - (double)alpha) * power_mag(co, dx, dy);
+                }
             for (uint32_t kk = last; kk-- > 0;) {
                 uint32_t id = point_list[beg + kk];
                 float dx = xy[2 * id] - pxf, dy = xy[2 * id + 1] - pyf;
@@ -594,6 +732,8 @@ int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
                 double mag_alpha = 0.0;   /* magnitude of dL_dalpha: sums of absolute values instead of differences */
                 double* a = acc + (size_t)id * 11;
                 double* ab = aab ? aab + (size_t)id * 11 : NULL;
+                double* ac = aac ? aac + (size_t)id * 10 : NULL;
+                const double wc = aac ? power_mag(co, dx, dy) + Upix : 0.0;
                 if (dL_dinvdepth_pix) {
                     float invd = 1.f / depths[id];
                     accum_invd = last_alpha * last_invd + (1.f - last_alpha) * accum_invd;
@@ -602,6 +742,7 @@ int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
                     mag_alpha += (fabs((double)invd) + fabs((double)accum_invd)) * fabs((double)dLd);
                     a[10] += (double)(dchannel_dcolor * dLd);
                     if (ab) ab[9] += wdepth * fabs((double)(dchannel_dcolor * dLd));
+                    if (ac) ac[9] += wc * fabs((double)(dchannel_dcolor * dLd));
                 }
                 for (int ch = 0; ch < 3; ++ch) {
                     float col = rgb[3 * id + ch];
@@ -611,6 +752,7 @@ int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
                     mag_alpha += (fabs((double)col) + fabs((double)accum_rec[ch])) * fabs((double)dLp[ch]);
                     a[6 + ch] += (double)(dchannel_dcolor * dLp[ch]);
                     if (ab) ab[6 + ch] += wdepth * fabs((double)(dchannel_dcolor * dLp[ch]));
+                    if (ac) ac[6 + ch] += wc * fabs((double)(dchannel_dcolor * dLp[ch]));
                 }
                 dL_dalpha *= T;
                 mag_alpha *= (double)T;
@@ -641,6 +783,17 @@ int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
                     ab[5] += wdepth * fabs((double)G) * mag_alpha;
                     ab[10] += 1.0;
                 }
+                if (ac) {
+                    const double mG = wc * fabs((double)co[3]) * mag_alpha;
+                    const double mx = fabs((double)(gdx * co[0])) + fabs((double)(gdy * co[1]));
+                    const double my = fabs((double)(gdy * co[2])) + fabs((double)(gdx * co[1]));
+                    ac[0] += mG * mx * (double)ddelx_dx;
+                    ac[1] += mG * my * (double)ddely_dy;
+                    ac[2] += fabs((double)(0.5f * gdx * dx)) * mG;
+                    ac[3] += fabs((double)(gdx * dy)) * mG;
+                    ac[4] += fabs((double)(0.5f * gdy * dy)) * mG;
+                    ac[5] += wc * fabs((double)G) * mag_alpha;
+                }
                 wdepth += 1.0;
             }
         }
@@ -652,10 +805,41 @@ int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
         dL_dopacity[i] = (float)a[5];
         for (int ch = 0; ch < 3; ++ch) dL_dcolor[3 * i + ch] = (float)a[6 + ch];
         if (abs_terms) for (int k = 0; k < 11; ++k) abs_terms[(size_t)i * 11 + k] = (float)aab[(size_t)i * 11 + k];
+        if (cond_terms) for (int k = 0; k < 10; ++k) cond_terms[(size_t)i * 10 + k] = (float)aac[(size_t)i * 10 + k];
     }
     free(acc);
     free(aab);
+    free(aac);
     return 0;
+}
+
+int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list,
+                   const float* xy, const float* conic_opacity, const float* rgb,
+                   const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
+                   float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                   float* abs_terms,
+                   const float* depths, const float* dL_dinvdepth_pix, float* dL_dinvdepth) {
+    return render_bwd_impl(c, ranges, point_list, xy, conic_opacity, rgb, final_T, n_contrib, dL_dpix, dL_dmean2D, dL_dconic,
+                           dL_dopacity, dL_dcolor, abs_terms, depths, dL_dinvdepth_pix, dL_dinvdepth, NULL);
+}
+
+/* hso_render_bwd that also returns cond_terms [P, 10]: the ten magnitude sums of abs_terms (same order, same |term|) with
+ * the weight w = M_i + U(pixel) in place of 4 + steps -- M_i of this (pixel, contributor), U = sum_j alpha_j / (1 - alpha_j) M_j
+ * over all contributors of the pixel (hso_threshold_risk_cond's T_units): per unit of 2^-24, how far the term may move
+ * between two fp32 evaluations of the power -- through G and alpha of the contributor itself (M_i) and through T and the
+ * accumulated colour behind it (U).  Tests add k 2^-24 sum w|term| to the bound of abs_terms (HSO_COND_K).  The gradients and
+ * abs_terms are those of hso_render_bwd bit for bit.  -1 when cond_terms is missing. */
+int hso_render_bwd_cond(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list,
+                        const float* xy, const float* conic_opacity, const float* rgb,
+                        const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
+                        float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                        float* abs_terms,
+                        const float* depths, const float* dL_dinvdepth_pix, float* dL_dinvdepth, float* cond_terms) {
+    if (!cond_terms || !c || !ranges || !point_list || !xy || !conic_opacity || !rgb || !final_T || !n_contrib || !dL_dpix ||
+        !dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor)
+        return -1;
+    return render_bwd_impl(c, ranges, point_list, xy, conic_opacity, rgb, final_T, n_contrib, dL_dpix, dL_dmean2D, dL_dconic,
+                           dL_dopacity, dL_dcolor, abs_terms, depths, dL_dinvdepth_pix, dL_dinvdepth, cond_terms);
 }
 
 /* ------------------------------------------------------------------------------------------

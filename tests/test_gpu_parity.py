@@ -1894,11 +1894,9 @@ EXTREME_SHARE = {"floaters": 0.965, "near_plane": 0.995, "off_screen": 0.98, "op
 def test_extreme_geometry_vs_oracle(oracle, name):
     """synthetic.extreme_scene: footprints that cover a 1080p frame (instance runs of 8160 tile records summed by one
     pair_segsum run), Gaussians at the near plane, centres frames away off screen, opaque stacks that terminate at varied
-    depths; and the floaters seen from eight rotating poses.  (Not here: needles -- scale ratios of 1e3-1e4 put the thin axis
-    at the 0.3 px dilation floor, and the power -0.5 d^T conic d then cancels terms of up to ~1e6 to a few units, so the
-    FMA-contracted kernel and the oracle decide alpha >= 1/255 differently on pixels outside oracle.threshold_risk's guard
-    band, which assumes a well-conditioned power: 13 pixels of a 960 x 540 frame.  The guard band needs the power's
-    conditioning first.)  Structure bit for bit against
+    depths; and the floaters seen from eight rotating poses.  (Needles and discs -- footprints whose power cancels terms far
+    larger than itself, which the fixed guard band used here does not cover -- are held to the oracle's CONDITIONED guard
+    band in tests/test_anisotropy_gpu.py.)  Structure bit for bit against
     the oracle, images off the pixels where a decision differs, gradients on the at-risk bars with the clear rows inside the
     per-element bound, and the masked pass: every row on the bar, every element inside the bound."""
     base = name.replace("_8_poses", "")
