@@ -7,12 +7,14 @@ Adam step that applies the gradients (optim.GaussianAdam), and the densify / pru
 changes the number of Gaussians under that optimizer (densify.densify_and_prune), and the neighbour
 distances that size a new cloud (knn.knn_mean_dist2, scene_io.init_from_points), and the MCMC policy's
 relocation, growth, position noise and regularisers (mcmc.relocate, mcmc.grow, mcmc.inject_noise, mcmc.regularize), and the
-3D smoothing filter of Mip-Splatting (smoothing.compute_filter_3D, GaussianRasterizer(..., filter_3D=...)).  Compute lives in
+3D smoothing filter of Mip-Splatting (smoothing.compute_filter_3D, GaussianRasterizer(..., filter_3D=...)), and the per-Gaussian
+blending-weight statistics contribution-based policies decide from (importance.accumulate_contributions).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
 """
 from .densify import DensifyResult, densify_and_prune
+from .importance import ContributionStats, accumulate_contributions
 from .knn import knn_mean_dist2
 from .losses import photometric_loss, ssim
 from .mcmc import GrowResult, RelocateResult, grow, inject_noise, regularize, relocate
@@ -25,5 +27,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats"
            "rasterize_gaussians", "inspect_state", "photometric_loss", "ssim", "GaussianAdam", "cloud_param_groups",
            "densify_and_prune", "DensifyResult", "knn_mean_dist2",
            "relocate", "grow", "inject_noise", "regularize", "RelocateResult", "GrowResult",
-           "compute_filter_3D", "apply_filter_3D"]
+           "compute_filter_3D", "apply_filter_3D", "ContributionStats", "accumulate_contributions"]
 __version__ = "0.1.0"

@@ -179,6 +179,11 @@ class hs_smoothing_apply_args(C.Structure):
                 ("dL_dopacities", _fp), ("dL_dscales", _fp)]
 
 
+class hs_contribution_args(C.Structure):
+    _fields_ = [("dims", hs_dims), ("geom", _fp), ("binning", _fp), ("image", _fp), ("ws", _fp), ("pixel_weight", _fp),
+                ("weight_sum", _fp), ("weight_max", _fp), ("pixel_count", _fp)]
+
+
 def _call(args):
     """int f(const args*, void* hip_stream): the shape of most entry points"""
     return C.c_int, [C.POINTER(args), C.c_void_p]
@@ -224,6 +229,8 @@ SIGNATURES = {
     "hs_smoothing_filter": _call(hs_smoothing_filter_args),
     "hs_smoothing_apply": _call(hs_smoothing_apply_args),
     "hs_smoothing_apply_backward": _call(hs_smoothing_apply_args),
+    "hs_contribution_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
+    "hs_contribution": _call(hs_contribution_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

@@ -874,6 +874,50 @@ typedef struct hs_knn_args {
 HS_API int64_t hs_knn_workspace_bytes(int64_t P);
 HS_API int hs_knn_mean_dist_sq(const hs_knn_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Per-Gaussian blending-weight statistics (contrib.hip): how much each Gaussian
+ * contributes to the images of a finished hs_forward call -- what contribution-based pruning (maximum alpha * T over the
+ * training rays), global significance scores (hit count, summed weight) and error-driven densification (sum over pixels of
+ * error * weight) decide from.  The quantity exists only inside the compositing loop: this is a front-to-back replay of the
+ * forward from the state it left in the three workspaces (rec, point_list, ranges, n_contrib, pair_act).  WHICH policy to
+ * run on the statistics stays with the trainer.
+ *
+ * Definition.  For one finished hs_forward call (HS_STAGE_ALL, or its stages in separate calls) with n_poses poses in
+ * F = max(n_frames, 1) frames: take every pose k, every pixel p and every entry g that the published rule composites at
+ * (k, p) -- power <= 0, alpha = min(0.99, o * e^power) >= 1 / 255, and the entry comes before the one at which
+ * T * (1 - alpha) < 1e-4 terminates the pixel -- with w = alpha * T_before and e = pixel_weight[frame(k), p] (1 when no weight
+ * image is given).  A pixel whose weight is exactly 0 takes part in nothing.  The call updates, IN PLACE like the
+ * densification statistics of hs_bwd_args:
+ *     weight_sum[g]  += sum of e * w                            (fp32)
+ *     weight_max[g]   = max(weight_max[g], max of e * w)        (fp32: starts from what the array holds)
+ *     pixel_count[g] += number of (k, p) with e * w > 0         (int32)
+ * No 1 / N normalisation.  Poses are folded into the running values one at a time in ascending pose order: a call over N poses
+ * leaves, bit for bit, what N single-pose calls leave.  A Gaussian no term reached keeps its three values bit for bit.  A
+ * call whose binning overflowed (hs_counters.overflow != 0) adds nothing -- decided on the device: nothing waits for the host.
+ *
+ * Three kernels on the caller's stream, no atomics: the replay (one 16-byte record {sum, max, count, 0} per (tile, instance)
+ * pair at the pair's duplicateWithKeys slot; the decisions are the forward's own -- the same alpha expressions, pair_act and
+ * n_contrib), a fixed-order sum of every instance's contiguous slots, the fold over the poses.  The same inputs give the same
+ * bits.  The workspace is separate from the four of hs_plan: hs_contribution_workspace_bytes(dims) = align256(16 * capacity)
+ * + align256(16 * P * n_poses) (256 when that is 0), 256-byte aligned; every word is written before it is read, so the result
+ * does not depend on what it held.  The three state workspaces are only read.
+ * HS_EINVAL (reported before any HIP call): null args; dims that hs_plan refuses; with P > 0 a null geom, binning, image, ws,
+ * weight_sum, weight_max or pixel_count (workspaces 256-byte, arrays 4-byte aligned).  P == 0 is a successful no-op. */
+typedef struct hs_contribution_args {
+    hs_dims dims;                 /* the dims of the hs_forward call */
+    const void* geom;             /* state produced by hs_forward (same buffers) */
+    const void* binning;
+    const void* image;
+    void* ws;                     /* hs_contribution_workspace_bytes(&dims) bytes, 256-byte aligned */
+    const float* pixel_weight;    /* [F,H,W] or NULL: every weight 1 */
+    float* weight_sum;            /* [P] */
+    float* weight_max;            /* [P] */
+    int32_t* pixel_count;         /* [P] */
+} hs_contribution_args;
+
+/* a positive multiple of 256, non-decreasing in capacity; -1 (HS_EINVAL) for dims that hs_plan refuses */
+HS_API int64_t hs_contribution_workspace_bytes(const hs_dims* dims);
+HS_API int hs_contribution(const hs_contribution_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
