@@ -8,7 +8,8 @@ changes the number of Gaussians under that optimizer (densify.densify_and_prune)
 distances that size a new cloud (knn.knn_mean_dist2, scene_io.init_from_points), and the MCMC policy's
 relocation, growth, position noise and regularisers (mcmc.relocate, mcmc.grow, mcmc.inject_noise, mcmc.regularize), and the
 3D smoothing filter of Mip-Splatting (smoothing.compute_filter_3D, GaussianRasterizer(..., filter_3D=...)), and the per-Gaussian
-blending-weight statistics contribution-based policies decide from (importance.accumulate_contributions).  Compute lives in
+blending-weight statistics contribution-based policies decide from (importance.accumulate_contributions), and the
+score-driven row edits that act on them (rows.prune_rows, rows.keep_top_k, rows.densify_top_k).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
@@ -21,11 +22,13 @@ from .mcmc import GrowResult, RelocateResult, grow, inject_noise, regularize, re
 from .optim import GaussianAdam, cloud_param_groups
 from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSettings, GaussianRasterizer,
                          SortChainStalled, inspect_state, rasterize_gaussians)
+from .rows import RowsResult, densify_top_k, keep_top_k, prune_rows
 from .smoothing import apply_filter_3D, compute_filter_3D
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats", "BinningOverflow", "SortChainStalled",
            "rasterize_gaussians", "inspect_state", "photometric_loss", "ssim", "GaussianAdam", "cloud_param_groups",
            "densify_and_prune", "DensifyResult", "knn_mean_dist2",
            "relocate", "grow", "inject_noise", "regularize", "RelocateResult", "GrowResult",
-           "compute_filter_3D", "apply_filter_3D", "ContributionStats", "accumulate_contributions"]
+           "compute_filter_3D", "apply_filter_3D", "ContributionStats", "accumulate_contributions",
+           "prune_rows", "keep_top_k", "densify_top_k", "RowsResult"]
 __version__ = "0.1.0"

@@ -133,6 +133,15 @@ class hs_densify_args(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+HS_ROWS_MASK, HS_ROWS_KEEP, HS_ROWS_DENSIFY = 0, 1, 2
+
+
+class hs_rows_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("k", C.c_int64), ("mode", C.c_int32), ("flags", C.c_int32), ("tau_split", C.c_float),
+                ("reserved", C.c_int32), ("score", _fp), ("mask", _fp), ("scales", _fp), ("workspace", _fp), ("row_map", _fp),
+                ("counts", _fp), ("counts_host", _fp)]
+
+
 class hs_activate_args(C.Structure):
     _fields_ = [("P", C.c_int64), ("g_begin", C.c_int64), ("g_end", C.c_int64),
                 ("opacity_raw", _fp), ("scales_raw", _fp), ("rotations_raw", _fp),
@@ -231,6 +240,8 @@ SIGNATURES = {
     "hs_smoothing_apply_backward": _call(hs_smoothing_apply_args),
     "hs_contribution_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
     "hs_contribution": _call(hs_contribution_args),
+    "hs_rows_workspace_bytes": (_i64, [_i64]),
+    "hs_rows_plan": _call(hs_rows_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

@@ -1,7 +1,7 @@
 // Densify / prune of the cloud (hs_densify_workspace_bytes, hs_densify_plan, hs_densify_apply; include/hdrsplat.h states the
 // contract and the policy, rule by rule).
 //
-// PLAN, three kernels:
+// PLAN, three kernels (the scan and the map live in hs_rowplan.h, which rows.hip includes too):
 //   densify_classify_kernel  one row per thread, 256 rows per workgroup: the row's 2-bit code
 //                                0 leaves nothing   1 survives   2 survives + one clone   3 goes, two children
 //                            as a byte of the workspace, and per workgroup four counts {survivors, clones, kept splits,
@@ -26,6 +26,7 @@
 // of a destination is written.  No atomics, no LDS in the apply; this file is compiled with -ffp-contract=off, and the order
 // of operations of a child's mean is the header's.
 #include "hs_cloud.h"
+#include "hs_rowplan.h"
 
 #include <math.h>
 #include <stddef.h>
@@ -34,8 +35,6 @@
 namespace hs {
 namespace {
 
-constexpr int kDenRows = 256;                 // rows per workgroup of the plan (= threads)
-constexpr int kDenScanThreads = 1024;
 constexpr int kDenThreads = 256;              // apply
 constexpr int kDenMaxGrid = 2048;             // 256 CUs x 8 workgroups; larger problems stride
 constexpr int kDenMaxMat = HS_DENSIFY_MAX_MATRICES;
@@ -85,79 +84,6 @@ __global__ void __launch_bounds__(kDenRows) densify_classify_kernel(const DenPla
         uint4 c = make_uint4(0u, 0u, 0u, 0u);
         for (int w = 0; w < kDenRows / 64; ++w) { c.x += s_cnt[w][0]; c.y += s_cnt[w][1]; c.z += s_cnt[w][2]; c.w += s_cnt[w][3]; }
         blocks[blockIdx.x] = c;
-    }
-}
-
-__device__ __forceinline__ uint4 add4(uint4 a, uint4 b) { return make_uint4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-
-__global__ void __launch_bounds__(kDenScanThreads) densify_scan_kernel(uint4* __restrict__ blocks, int64_t nblk, uint32_t P,
-                                                                        uint32_t* __restrict__ counts) {
-    __shared__ uint4 s_part[kDenScanThreads];
-    const int t = threadIdx.x;
-    const int64_t per = (nblk + kDenScanThreads - 1) / kDenScanThreads;
-    const int64_t b0 = t * per < nblk ? t * per : nblk, b1 = b0 + per < nblk ? b0 + per : nblk;
-    uint4 acc = make_uint4(0u, 0u, 0u, 0u);
-    for (int64_t b = b0; b < b1; ++b) acc = add4(acc, blocks[b]);
-    s_part[t] = acc;
-    __syncthreads();
-    for (int off = 1; off < kDenScanThreads; off <<= 1) {
-        const uint4 v = t >= off ? s_part[t - off] : make_uint4(0u, 0u, 0u, 0u);
-        __syncthreads();
-        s_part[t] = add4(s_part[t], v);
-        __syncthreads();
-    }
-    uint4 run = t ? s_part[t - 1] : make_uint4(0u, 0u, 0u, 0u);
-    for (int64_t b = b0; b < b1; ++b) {
-        const uint4 c = blocks[b];
-        blocks[b] = run;
-        run = add4(run, c);
-    }
-    if (t == kDenScanThreads - 1) {
-        const uint4 tot = s_part[t];      // {survivors, clones, kept splits, split sources}
-        counts[0] = tot.x + tot.y + 2u * tot.z;
-        counts[1] = tot.x;
-        counts[2] = tot.y;
-        counts[3] = 2u * tot.z;
-        counts[4] = P - tot.x - tot.z;
-        counts[5] = tot.w;
-        counts[6] = P;
-        counts[7] = 0u;
-    }
-}
-
-__global__ void __launch_bounds__(kDenRows) densify_map_kernel(const uint8_t* __restrict__ codes, const uint4* __restrict__ prefix,
-                                                               int64_t P, const uint32_t* __restrict__ counts,
-                                                               uint32_t* __restrict__ row_map, uint32_t* counts_host) {
-    __shared__ uint32_t s_cnt[kDenRows / 64][3];
-    if (counts_host && blockIdx.x == 0 && threadIdx.x < HS_DENSIFY_COUNTS)   // (the stage's last kernel, as tile_ranges_kernel is)
-        __hip_atomic_store(counts_host + threadIdx.x, counts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (P == 0) return;
-    const int64_t i = (int64_t)blockIdx.x * kDenRows + threadIdx.x;
-    const uint32_t code = i < P ? codes[i] : 0u;
-    const bool surv = code == 1u || code == 2u, clone = code == 2u, kept = code == 3u;
-    const unsigned long long b_surv = __ballot(surv), b_clone = __ballot(clone), b_kept = __ballot(kept);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        s_cnt[wave][0] = (uint32_t)__popcll(b_surv);
-        s_cnt[wave][1] = (uint32_t)__popcll(b_clone);
-        s_cnt[wave][2] = (uint32_t)__popcll(b_kept);
-    }
-    __syncthreads();
-    const uint4 pre = prefix[blockIdx.x];
-    uint32_t js = pre.x, jc = pre.y, jk = pre.z;
-    for (int w = 0; w < wave; ++w) { js += s_cnt[w][0]; jc += s_cnt[w][1]; jk += s_cnt[w][2]; }
-    const unsigned long long below = (1ull << lane) - 1ull;
-    js += (uint32_t)__popcll(b_surv & below);
-    jc += (uint32_t)__popcll(b_clone & below);
-    jk += (uint32_t)__popcll(b_kept & below);
-    const uint32_t n_surv = counts[1], n_clone = counts[2], n_kept = counts[3] >> 1;
-    const uint32_t src = (uint32_t)i;
-    // (every index is below P_out = n_surv + n_clone + 2 n_kept <= 2 P: the prefixes and totals count the same codes)
-    if (surv) row_map[js] = ((uint32_t)HS_DENSIFY_KIND_SURVIVOR << 30) | src;
-    if (clone) row_map[n_surv + jc] = ((uint32_t)HS_DENSIFY_KIND_CLONE << 30) | src;
-    if (kept) {
-        row_map[n_surv + n_clone + jk] = ((uint32_t)HS_DENSIFY_KIND_CHILD0 << 30) | src;
-        row_map[n_surv + n_clone + n_kept + jk] = ((uint32_t)HS_DENSIFY_KIND_CHILD1 << 30) | src;
     }
 }
 
@@ -336,8 +262,6 @@ int check_apply_args(const hs_densify_args* a) {
     const Field in[] = {{a->scales, "scales", 4}, {a->rotations, "rotations", 4}, {a->noise, "noise", 4}};
     return check_fields(fn, in, 3, " (read by the HS_DENSIFY_MEANS role)");
 }
-
-inline int64_t den_blocks(int64_t P) { return (P + kDenRows - 1) / kDenRows; }
 
 int launch_plan(const hs_densify_args& a, hipStream_t s) {
     DenPlan p;

@@ -132,6 +132,65 @@ def _check_stats(stats, P: int, dev) -> None:
             raise ValueError(f"densify_and_prune: stats.{what} must be a contiguous {dt} tensor [{P}] on the cloud's device")
 
 
+def _cloud_matrices(what, optimizer, cloud, P, children) -> list:
+    """The cloud's matrices of one gather, in the order of the optimizer's groups: (cloud name, parameter, exp_avg,
+    exp_avg_sq, floats per row, role of the parameter).  `children`: the plan may hold split children, so the means and
+    scales take the MEANS and SCALES roles; otherwise every parameter is copied."""
+    out, seen = [], set()
+    for g in optimizer.param_groups:
+        name = g.get("name")
+        if name not in _GROUPS:
+            continue
+        key, _, role = _GROUPS[name]
+        if key in seen:
+            continue
+        seen.add(key)
+        p = cloud[key]
+        st = optimizer._init_state(p)
+        m, v = st["exp_avg"], st["exp_avg_sq"]
+        for t in (m, v):
+            _require_gpu(t, "every moment tensor")
+            if t.dtype != torch.float32 or t.shape != p.shape or not t.is_contiguous() or t.device != p.device:
+                raise ValueError(f"{what}: exp_avg / exp_avg_sq must be contiguous float32 tensors of their parameter's shape")
+        stride = p.numel() // P if P else max(1, math.prod(p.shape[1:]))
+        out.append((key, p, m, v, stride, role if children else L.HS_DENSIFY_COPY))
+    return out
+
+
+def _gather_rows(optimizer, cloud, specs, dsts, P, P_out, row_map, flags, noise=None, extras=()) -> dict:
+    """The second half of every edit of the cloud's rows: hs_densify_apply over the matrices of `specs` (_cloud_matrices)
+    into `dsts` (per spec: new parameter, exp_avg, exp_avg_sq, [P_out, ...], allocated by the caller) and over `extras`
+    (pairs (source, destination) of 4-byte element tensors, COPY role), HS_DENSIFY_MAX_MATRICES per launch; then the new
+    tensors take the old ones' places in the optimizer (GaussianAdam.replace_params).  Returns CLOUD_NAMES -> new leaf."""
+    dev = cloud["means3D"].device
+    mats = []
+    for (_, p, m, v, stride, role), (np_, nm, nv) in zip(specs, dsts):
+        mats += [(p, np_, stride, role), (m, nm, stride, L.HS_DENSIFY_ZERO_NEW), (v, nv, stride, L.HS_DENSIFY_ZERO_NEW)]
+    for src, dst in extras:
+        mats.append((src, dst, src.numel() // P if P else max(1, math.prod(src.shape[1:])), L.HS_DENSIFY_COPY))
+    lib = L.load()
+    a = L.hs_densify_args()
+    a.P, a.P_out, a.flags, a.row_map = P, P_out, flags, row_map.data_ptr()
+    a.scales, a.rotations = cloud["scales"].data_ptr(), cloud["rotations"].data_ptr()
+    a.noise = None if noise is None else noise.data_ptr()
+    with _on_device(dev):
+        for first in range(0, len(mats), L.HS_DENSIFY_MAX_MATRICES):
+            part = mats[first:first + L.HS_DENSIFY_MAX_MATRICES]
+            arr = (L.hs_densify_matrix * len(part))()
+            for d, (src, dst, stride, role) in zip(arr, part):
+                d.src, d.dst, d.row_stride, d.role = src.data_ptr(), dst.data_ptr(), stride, role
+            a.matrices, a.n_matrices = arr, len(part)
+            L.check(lib.hs_densify_apply(C.byref(a), _stream(dev)), "hs_densify_apply")
+    by_key = {spec[0]: dst for spec, dst in zip(specs, dsts)}
+    new, mapping = {}, {}
+    for key in CLOUD_NAMES:
+        old = cloud[key]
+        new[key] = by_key[key][0].requires_grad_(old.requires_grad)
+        mapping[old] = by_key[key]
+    optimizer.replace_params(mapping)
+    return new
+
+
 def densify_and_prune(optimizer, stats, *, extent, grad_threshold=2e-4, percent_dense=0.01, min_opacity=0.005,
                       max_screen_size=None, raw_scales=True, raw_opacity=True, generator=None, noise=None) -> DensifyResult:
     """One densification of the cloud `optimizer` updates, from the statistics `stats` collected since the last one.
@@ -179,39 +238,13 @@ def densify_and_prune(optimizer, stats, *, extent, grad_threshold=2e-4, percent_
     P_out = got[0]
 
     # the five tensors and their moments: at most 15 matrices, one launch
-    new, moments, mats = {}, {}, []
-    for g in optimizer.param_groups:
-        name = g.get("name")
-        if name not in _GROUPS:
-            continue
-        key, _, role = _GROUPS[name]
-        if key in new:
-            continue
-        p = cloud[key]
-        st = optimizer._init_state(p)
-        m, v = st["exp_avg"], st["exp_avg_sq"]
-        for t in (m, v):
-            _require_gpu(t, "every moment tensor")
-            if t.dtype != torch.float32 or t.shape != p.shape or not t.is_contiguous() or t.device != dev:
-                raise ValueError("densify_and_prune: exp_avg / exp_avg_sq must be contiguous float32 tensors of their parameter's shape")
+    specs = _cloud_matrices("densify_and_prune", optimizer, cloud, P, children=True)
+    dsts = []
+    # (allocated by the caller of the gather: the poisoned-buffer tests name a buffer by the function that asked for it)
+    for _, p, _, _, _, _ in specs:
         shape = (P_out,) + tuple(p.shape[1:])
-        stride = p.numel() // P if P else max(1, math.prod(p.shape[1:]))
-        new[key] = torch.empty(shape, dtype=torch.float32, device=dev)
-        moments[key] = (torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev))
-        mats += [(p, new[key], stride, role), (m, moments[key][0], stride, L.HS_DENSIFY_ZERO_NEW),
-                 (v, moments[key][1], stride, L.HS_DENSIFY_ZERO_NEW)]
-    arr = (L.hs_densify_matrix * len(mats))()
-    for d, (src, dst, stride, role) in zip(arr, mats):
-        d.src, d.dst, d.row_stride, d.role = src.data_ptr(), dst.data_ptr(), stride, role
-    a.P_out, a.matrices, a.n_matrices = P_out, arr, len(mats)
-    with _on_device(dev):
-        L.check(lib.hs_densify_apply(C.byref(a), _stream(dev)), "hs_densify_apply")
-
-    mapping = {}
-    for key in CLOUD_NAMES:
-        old = cloud[key]
-        new[key].requires_grad_(old.requires_grad)
-        mapping[old] = (new[key], *moments[key])
-    optimizer.replace_params(mapping)
+        dsts.append((torch.empty(shape, dtype=torch.float32, device=dev), torch.empty(shape, dtype=torch.float32, device=dev),
+                     torch.empty(shape, dtype=torch.float32, device=dev)))
+    new = _gather_rows(optimizer, cloud, specs, dsts, P, P_out, row_map, th["flags"], noise)
     stats.resize(P_out)
     return DensifyResult(params={k: new[k] for k in CLOUD_NAMES}, counts=dict(zip(COUNT_NAMES, got)), row_map=row_map[:P_out])

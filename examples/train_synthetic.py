@@ -15,6 +15,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --batch-frames         # all frames of a step in ONE rasterizer call
     python examples/train_synthetic.py --steps 300 --mcmc                 # learn the WHOLE cloud from a quarter of the points: MCMC policy
     python examples/train_synthetic.py --steps 300 --mcmc --filter-3d     # ... with the 3D smoothing filter of Mip-Splatting
+    python examples/train_synthetic.py --steps 300 --topk                 # ... grown by score to a budget, pruned by contribution
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -33,12 +34,14 @@ import torch
 
 from casualhdrsplat_amd import scene_io
 from casualhdrsplat_amd import synthetic as S
+from casualhdrsplat_amd.importance import ContributionStats, accumulate_contributions
 from casualhdrsplat_amd.mcmc import grow, inject_noise, regularize, relocate
+from casualhdrsplat_amd.rows import densify_top_k, keep_top_k
 from casualhdrsplat_amd.optim import cloud_param_groups
 from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.optim import GaussianAdam
 from casualhdrsplat_amd.graphs import GraphedStep
-from casualhdrsplat_amd.rasterizer import GaussianRasterizer
+from casualhdrsplat_amd.rasterizer import DensifyStats, GaussianRasterizer
 from casualhdrsplat_amd.image_formation import (FrameRasterizers, HDRBlurFormation, ImplicitCRF, TrajectorySpline,
                                                   knots_from_lookat)
 
@@ -64,7 +67,7 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
-        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False):
+        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -89,13 +92,28 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     filter_3d (with mcmc): the 3D smoothing filter of Mip-Splatting.  HDRBlurFormation.compute_filter_3D computes it from every
     virtual pose of the learner's trajectory at the start and again after every grow (the rows moved and P changed), and the
     learner's rasterizers fold it into the opacities and scales they run on (GaussianRasterizer.filter_3D); the optimizer, the
-    regularisers and the relocation keep working on the stored tensors.  The history gains the filter's length."""
+    regularisers and the relocation keep working on the stored tensors.  The history gains the filter's length.
+    topk: the learner of mcmc (P // 4 noised points, all five stored tensors under one GaussianAdam, raw rasterizers) under a
+    score-driven, budgeted policy instead: its rasterizers collect a DensifyStats, and every `refine_every` steps
+    rows.densify_top_k clones or splits the k = min(cap - P, round(P (factor - 1))) rows with the largest mean view-space
+    gradient, under the factor schedule of mcmc -- the host knows the new size, nothing is read back.  At the last refinement,
+    after the growth, a no_grad pass over all frames accumulates the blending-weight statistics
+    (importance.accumulate_contributions) and rows.keep_top_k keeps the P - P // 10 rows with the largest maximum weight.  No
+    noise, no regularisers, no relocation.  Eager only; not together with mcmc.  The history gains P."""
+    if topk and mcmc:
+        raise ValueError("topk=True (--topk) and mcmc=True (--mcmc) are two refinement policies for the same learner: choose one")
+    if topk and graph:
+        raise ValueError("topk=True (--topk) is not supported together with graph=True (--graph): the number of Gaussians "
+                         "changes at every refinement, a captured step is recorded for one size")
+    if topk and filter_3d:
+        raise ValueError("filter_3d=True (--filter-3d) needs mcmc=True (--mcmc)")
     if filter_3d and not mcmc:
         raise ValueError("filter_3d=True (--filter-3d) needs mcmc=True (--mcmc): the other modes hold the scales at the truth")
     if mcmc and graph:
         raise ValueError("mcmc=True (--mcmc) is not supported together with graph=True (--graph): the number of Gaussians "
                          "changes at every refinement, a captured step is recorded for one size")
-    if mcmc:
+    whole = mcmc or topk                # the learner does not know the cloud: all five stored tensors are leaves
+    if whole:
         fused_adam = raw = True
     if batch_frames and graph:
         raise ValueError("batch_frames=True (--batch-frames) is not supported together with graph=True (--graph): the captured "
@@ -130,6 +148,12 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     if filter_3d:
         def factory(settings):
             return GaussianRasterizer(settings, filter_3D=filt["filter_3D"], **how)
+    score = {"stats": None, "keep_state": False, "last": None}     # --topk: the statistics its rasterizers collect
+    if topk:
+        def factory(settings):
+            score["last"] = GaussianRasterizer(settings, densify_stats=None if score["keep_state"] else score["stats"],
+                                               keep_state=score["keep_state"], **how)
+            return score["last"]
     model = formation(ImplicitCRF(K=128), **({"rasterizer_factory": factory} if factory is not None else {}))
     model.crf.load_state_dict(truth.crf.state_dict())
     for p_ in model.crf.parameters():
@@ -147,7 +171,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     cur = {"means3D": fixed["means3D"], "opacities": raw_opac, "shs": shs, "scales": fixed["scales"], "rotations": fixed["rotations"]}
     with torch.no_grad():
         model.log_exposure[0] = truth.log_exposure[0]       # the gauge (see the module docstring)
-    if mcmc:
+    if whole:
         P0 = max(P // 4, 4)
         pick = torch.randperm(P, generator=gen)[:P0]
         xyz0 = sc.means3D[pick] + 0.02 * torch.randn(P0, 3, generator=gen)
@@ -164,6 +188,9 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         gen_dev = torch.Generator(device=dev).manual_seed(seed + 3)
         if filter_3d:
             filt["filter_3D"] = model.compute_filter_3D(cur["means3D"])
+        if topk:
+            score["stats"] = DensifyStats(P0, dev)
+            extent = float(sc.means3D.std(dim=0).norm())
     elif fused_adam:
         opt = GaussianAdam([
             {"params": [shs], "lr": 1e-2, "per_gaussian": True}, {"params": [raw_opac], "lr": 2e-2, "per_gaussian": True},
@@ -181,7 +208,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             return e_dt, e_pose
 
     learn = [shs, raw_opac, model.log_exposure, model.trajectory.delta]
-    if mcmc:
+    if whole:
         learn = [cur[k] for k in CLOUD] + [model.log_exposure, model.trajectory.delta]
 
     def gradients():
@@ -195,7 +222,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         losses, mses = [], []
         for i in range(frames):
             ldr, _, radii, _ = model(i, cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"], cameras=cams)
-            if fused_adam and not mcmc:   # (kernels only, written in place: the captured step leaves no copy node behind)
+            if fused_adam and not whole:   # (kernels only, written in place: the captured step leaves no copy node behind)
                 if i == 0:
                     torch.gt(radii, 0, out=seen)
                 else:
@@ -218,7 +245,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             p_.grad = None
         opac = cur["opacities"] if raw else torch.sigmoid(raw_opac)
         ldr, _, radii, _ = model.forward_frames(range(frames), cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"])
-        if fused_adam and not mcmc:
+        if fused_adam and not whole:
             torch.gt(radii, 0, out=seen)      # (radii: the maximum over every frame's poses)
         if lambda_dssim > 0:
             # (one fused loss over the [frames, 3, H, W] batch: it averages over every plane, i.e. it is the MEAN of the
@@ -257,6 +284,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             total += frames * (terms[0] + terms[1])
             if filter_3d:
                 extra["filter_len"] = int(filt["filter_3D"].shape[0])
+        if topk:
+            extra = dict(P=int(cur["means3D"].shape[0]))
         if it < steps:
             g0 = model.log_exposure.grad
             if g0 is not None:
@@ -273,6 +302,28 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                     learn[:len(CLOUD)] = [cur[k] for k in CLOUD]
                     if filter_3d:                              # (the rows moved and P changed: the filter follows)
                         filt["filter_3D"] = model.compute_filter_3D(cur["means3D"])
+            elif topk:
+                opt.step()
+                if it in refine_at:
+                    P_now, left = int(cur["means3D"].shape[0]), len(refine_at) - refine_at.index(it)
+                    factor = min(2.0, max(1.0, (cap / P_now) ** (1.0 / left) * (1.0 + 1e-12)))
+                    k = min(cap - P_now, int(round(P_now * (factor - 1.0))))
+                    res = densify_top_k(opt, score["stats"].mean_grad(), k, extent=extent, generator=gen_dev)
+                    score["stats"].resize(res.P_out)
+                    if it == refine_at[-1]:                    # the final prune: by contribution, to nine tenths
+                        cstats = ContributionStats(res.P_out, dev)
+                        score["keep_state"] = True
+                        with torch.no_grad():
+                            cams = model.cameras_all()
+                            q = res.params
+                            for i in range(frames):
+                                model(i, q["means3D"], q["opacities"], q["shs"], q["scales"], q["rotations"], cameras=cams)
+                                accumulate_contributions(score["last"], cstats)
+                        score["keep_state"] = False
+                        res = keep_top_k(opt, cstats.weight_max, res.P_out - res.P_out // 10)
+                        score["stats"].resize(res.P_out)
+                    cur.update(res.params)
+                    learn[:len(CLOUD)] = [cur[k] for k in CLOUD]
             elif fused_adam:
                 opt.step(visibility=seen)
             else:
@@ -282,9 +333,10 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         if not quiet and (it % log_every == 0 or it == steps):
             print(f"step {it:4d}  {'L1' if lambda_dssim == 0 else 'loss'} {total / frames:.5f}  PSNR {ps / frames:6.2f} dB  |log dt - truth| {e_dt:.4f}  "
                   f"knot position error {e_pose:.5f}  ({(time.time() - t0) / max(it, 1) * 1e3:.1f} ms/step)" +
-                  (f"  P {extra['P']}  regularisers {extra['reg_opacity']:.5f} + {extra['reg_scale']:.5f}" if mcmc else ""))
+                  (f"  P {extra['P']}  regularisers {extra['reg_opacity']:.5f} + {extra['reg_scale']:.5f}" if mcmc else "") +
+                  (f"  P {extra['P']}" if topk else ""))
     out = dict(first=hist[0], last=hist[-1], history=hist)
-    if mcmc:
+    if whole:
         out["cloud"] = {k: cur[k].detach() for k in CLOUD}
         if filter_3d:
             out["filter_3D"] = filt["filter_3D"]
@@ -320,6 +372,11 @@ def main(argv=None):
     ap.add_argument("--filter-3d", action="store_true",
                     help="--mcmc: the 3D smoothing filter of Mip-Splatting, computed from every virtual pose at the start and after "
                          "every grow and folded into the opacities and scales the rasterizers run on")
+    ap.add_argument("--topk", action="store_true",
+                    help="learn the whole cloud from P / 4 noised points under a score-driven budget: every --refine-every steps "
+                         "densify_top_k clones / splits the rows with the largest mean view-space gradient towards --cap-max, and the "
+                         "last refinement keeps the nine tenths with the largest blending weight (keep_top_k); eager only, not "
+                         "with --mcmc")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
@@ -327,7 +384,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
-            refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d)
+            refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

@@ -582,6 +582,66 @@ HS_API int64_t hs_densify_workspace_bytes(int64_t P);
 HS_API int hs_densify_plan(const hs_densify_args* args, void* hip_stream);
 HS_API int hs_densify_apply(const hs_densify_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Score-driven row plans of the cloud (rows.hip): prune by a mask, keep the k best
+ * rows, or clone / split the k best rows -- the PLAN stage of a refinement whose policy is the caller's score.  The output is
+ * hs_densify_plan's, so the unchanged hs_densify_apply gathers from it.  In KEEP and DENSIFY mode the host knows P_out before
+ * any kernel runs (k, and P + k: a clone adds one row, a split removes one and adds two), so nothing has to be read back.  The
+ * caller owns every byte; nothing here synchronises, allocates, sets or copies memory.  No float arithmetic and no float or
+ * global atomics: the same inputs give the same bits.
+ *
+ * THE ORDER ON SCORES (fp32 `score`, [P]):
+ *   1. NaN ranks below every number, and all NaNs are equal;
+ *   2. -0 equals +0;
+ *   3. everything else is in numeric order, +-infinity and denormals in their places.
+ * "The k best rows" are the first k rows when all rows are listed by (score descending, row index ascending): among equal
+ * scores the lower row wins.  T = the number of rows whose score equals the k-th best one (0 when k == 0).
+ *
+ *   HS_ROWS_MASK     rows with mask[i] != 0 leave, the others survive; P_out = counts[0], which the caller reads
+ *   HS_ROWS_KEEP     the k best rows survive, the others leave; P_out = k
+ *   HS_ROWS_DENSIFY  every selected row i, with s the maximum of its three stored scales by hs_densify_plan's comparisons
+ *                    (s = scales[3i]; if (scales[3i+1] > s) s = scales[3i+1]; the same for [3i+2]), is SPLIT when
+ *                    s > tau_split (the source goes, children k = 0, 1) and CLONED otherwise (the row survives and a copy is
+ *                    appended); rows not selected survive; nothing is pruned; P_out = P + k.  tau_split is compared AS STORED
+ *                    (a log with HS_DENSIFY_RAW_SCALES; the flag is what the caller hands hs_densify_apply with the plan)
+ *
+ * Output, exactly hs_densify_plan's: row_map[j] = kind << 30 | source row for j < P_out, segments survivors | clones | children
+ * k = 0 | children k = 1, each in source order, and counts[HS_DENSIFY_COUNTS] (u32) = {P_out, survivors, clones, children (both
+ * k), sources that left no row, split sources, P, T}; a copy at counts_host (NULL, or a page-locked host address as
+ * hs_densify_args.counts_host is), written by the call's last kernel.  row_map holds P u32 in MASK and KEEP mode, P + k in
+ * DENSIFY mode; nothing is written at or beyond row P_out.
+ *
+ * Kernels: with k > 0 an exact radix select over the 32-bit key of the order (four passes of a histogram over contiguous
+ * chunks of rows and a one-workgroup pick, most significant byte first) finds the k-th best key and the number of rows strictly
+ * above it; one classify pass (a row is selected above the threshold, or at it while its rank among the threshold rows, in
+ * source order, is below k - above); then the scan and the map of the densify plan.  3 launches in MASK mode, 12 otherwise.
+ * Workspace: hs_rows_workspace_bytes(P) = align256(P) + align256(16 * ceil(P / 256)) + 263424 bytes, 16-byte aligned; every
+ * word is written before it is read.
+ * Limits (HS_EINVAL, reported before any HIP call): 0 <= P < 2^30; 0 <= k <= P; mode one of HS_ROWS_*; flags within
+ * HS_DENSIFY_RAW_SCALES; tau_split not NaN (DENSIFY); the pointers the mode reads non-null and 4-byte aligned (mask: any
+ * address; workspace: 16 bytes); with P == 0 no data pointer is looked at (counts is still written). */
+#define HS_ROWS_MASK 0
+#define HS_ROWS_KEEP 1
+#define HS_ROWS_DENSIFY 2
+typedef struct hs_rows_args {
+    int64_t P;                    /* rows */
+    int64_t k;                    /* KEEP: rows that stay; DENSIFY: rows cloned or split; MASK: 0 */
+    int32_t mode;                 /* HS_ROWS_MASK / _KEEP / _DENSIFY */
+    int32_t flags;                /* HS_DENSIFY_RAW_SCALES only */
+    float tau_split;              /* DENSIFY, stored space: split above, clone at or below */
+    int32_t reserved;
+    const float* score;           /* [P]     KEEP, DENSIFY */
+    const uint8_t* mask;          /* [P]     MASK */
+    const float* scales;          /* [P, 3]  DENSIFY: clone or split */
+    void* workspace;              /* hs_rows_workspace_bytes(P) bytes, 16-byte aligned */
+    uint32_t* row_map;            /* [P] (MASK, KEEP) or [P + k] (DENSIFY): hs_densify_apply's row_map */
+    uint32_t* counts;             /* device, [HS_DENSIFY_COUNTS] */
+    uint32_t* counts_host;        /* NULL, or a page-locked host address the GPU can write: the copy of counts */
+} hs_rows_args;
+
+/* the formula above; -1 (HS_EINVAL) unless 0 <= P < 2^30 */
+HS_API int64_t hs_rows_workspace_bytes(int64_t P);
+HS_API int hs_rows_plan(const hs_rows_args* args, void* hip_stream);
+
 /* (detected by name; HS_VERSION unchanged) MCMC refinement of the cloud (mcmc.hip): the relocation, the growth and the
  * position noise of "3D Gaussian Splatting as Markov Chain Monte Carlo".  A fixed row budget, a size the host knows before
  * any kernel runs, and dead rows moved onto live ones in place: nothing here is read back, nothing synchronises, allocates,
