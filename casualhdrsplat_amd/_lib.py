@@ -193,6 +193,13 @@ class hs_contribution_args(C.Structure):
                 ("weight_sum", _fp), ("weight_max", _fp), ("pixel_count", _fp)]
 
 
+class hs_abs_gradient_args(C.Structure):
+    _fields_ = [("dims", hs_dims), ("flags", C.c_int32), ("crf_K", C.c_int32), ("crf_umin", C.c_float), ("crf_umax", C.c_float),
+                ("bg", _fp), ("exposure", _fp), ("crf_table", _fp), ("geom", _fp), ("binning", _fp), ("image", _fp), ("ws", _fp),
+                ("dL_dout_color", _fp), ("dL_dout_hdr", _fp), ("dL_dout_alpha", _fp), ("dL_dout_invdepth", _fp),
+                ("abs_grad_accum", _fp)]
+
+
 def _call(args):
     """int f(const args*, void* hip_stream): the shape of most entry points"""
     return C.c_int, [C.POINTER(args), C.c_void_p]
@@ -240,6 +247,8 @@ SIGNATURES = {
     "hs_smoothing_apply_backward": _call(hs_smoothing_apply_args),
     "hs_contribution_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
     "hs_contribution": _call(hs_contribution_args),
+    "hs_abs_gradient_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
+    "hs_abs_gradient": _call(hs_abs_gradient_args),
     "hs_rows_workspace_bytes": (_i64, [_i64]),
     "hs_rows_plan": _call(hs_rows_args),
 }

@@ -192,15 +192,28 @@ def _gather_rows(optimizer, cloud, specs, dsts, P, P_out, row_map, flags, noise=
 
 
 def densify_and_prune(optimizer, stats, *, extent, grad_threshold=2e-4, percent_dense=0.01, min_opacity=0.005,
-                      max_screen_size=None, raw_scales=True, raw_opacity=True, generator=None, noise=None) -> DensifyResult:
+                      max_screen_size=None, raw_scales=True, raw_opacity=True, generator=None, noise=None,
+                      absgrad=False) -> DensifyResult:
     """One densification of the cloud `optimizer` updates, from the statistics `stats` collected since the last one.
     Returns the new leaf tensors by name, the counts and the row map; the optimizer holds the new tensors (their moments
     gathered, zero for new rows, step count and running products untouched) and `stats` is zeroed at the new size.
-    `noise` ([P, 2, 3] float32 on the device) replaces the draw from `generator`."""
+    `noise` ([P, 2, 3] float32 on the device) replaces the draw from `generator`.  absgrad=True: the gradient test reads
+    `stats.abs_grad_accum` (the AbsGS statistic, DensifyStats(absgrad=True)) where it otherwise reads `stats.grad_accum` --
+    the same kernels, another array; `grad_threshold` stays the caller's (AbsGS trainers raise it)."""
     cloud = _cloud_of(optimizer)
     P = int(cloud["means3D"].shape[0])
     dev = cloud["means3D"].device
     _check_stats(stats, P, dev)
+    grad_accum = stats.grad_accum
+    if absgrad:
+        grad_accum = stats.abs_grad_accum
+        if grad_accum is None:
+            raise ValueError("densify_and_prune: absgrad=True needs stats.abs_grad_accum: create the statistics with "
+                             "DensifyStats(P, device, absgrad=True)")
+        _require_gpu(grad_accum, "stats.abs_grad_accum")
+        if grad_accum.dtype != torch.float32 or grad_accum.shape != (P,) or grad_accum.device != dev or not grad_accum.is_contiguous():
+            raise ValueError(f"densify_and_prune: stats.abs_grad_accum must be a contiguous {torch.float32} tensor [{P}] on the "
+                             "cloud's device")
     th = stored_thresholds(float(extent), float(grad_threshold), float(percent_dense), float(min_opacity), max_screen_size,
                            bool(raw_scales), bool(raw_opacity))
     if P >= 1 << 30:
@@ -224,7 +237,7 @@ def densify_and_prune(optimizer, stats, *, extent, grad_threshold=2e-4, percent_
     a.P, a.P_out = P, 0
     for k, v in th.items():
         setattr(a, k, v)
-    a.grad_accum, a.denom, a.max_radii = stats.grad_accum.data_ptr(), stats.denom.data_ptr(), stats.max_radii.data_ptr()
+    a.grad_accum, a.denom, a.max_radii = grad_accum.data_ptr(), stats.denom.data_ptr(), stats.max_radii.data_ptr()
     a.opacities, a.scales = cloud["opacities"].data_ptr(), cloud["scales"].data_ptr()
     a.rotations, a.noise = cloud["rotations"].data_ptr(), noise.data_ptr()
     a.workspace, a.row_map = workspace.data_ptr(), row_map.data_ptr()

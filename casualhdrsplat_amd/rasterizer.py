@@ -150,18 +150,31 @@ class _State:
 class DensifyStats:
     """Per-Gaussian statistics a 3DGS trainer keeps between densification rounds, updated inside
     the backward kernel of every GaussianRasterizer call that was given this object: `grad_accum` += |means2D.grad.xy|,
-    `denom` += 1 and `max_radii` = max(max_radii, radii), for the Gaussians rasterized in that call."""
+    `denom` += 1 and `max_radii` = max(max_radii, radii), for the Gaussians rasterized in that call.
 
-    def __init__(self, P: int, device="cuda"):
+    absgrad=True: it also owns `abs_grad_accum` (float32 [P]; None otherwise), the AbsGS statistic -- per call and frame,
+    += the length of (sum over pixels of |x term|, sum over pixels of |y term|) of dL/dmeans2D, where `grad_accum` takes the
+    length of the signed sums.  Every backward of a rasterizer given this object then enqueues one replay of the frame
+    behind its render stage (importance.py; include/hdrsplat.h, hs_abs_gradient); `denom` is shared."""
+
+    def __init__(self, P: int, device="cuda", absgrad: bool = False):
         self.grad_accum = torch.zeros(P, dtype=torch.float32, device=device)
         self.denom = torch.zeros(P, dtype=torch.float32, device=device)
         self.max_radii = torch.zeros(P, dtype=torch.int32, device=device)
+        self.abs_grad_accum = torch.zeros(P, dtype=torch.float32, device=device) if absgrad else None
 
     def mean_grad(self) -> torch.Tensor:
         return self.grad_accum / self.denom.clamp_min(1.0)
 
+    def mean_abs_grad(self) -> torch.Tensor:
+        if self.abs_grad_accum is None:
+            raise ValueError("DensifyStats.mean_abs_grad: created without absgrad=True")
+        return self.abs_grad_accum / self.denom.clamp_min(1.0)
+
     def reset(self) -> None:
         self.grad_accum.zero_(); self.denom.zero_(); self.max_radii.zero_()
+        if self.abs_grad_accum is not None:
+            self.abs_grad_accum.zero_()
 
     def resize(self, P: int) -> None:
         """Zeroed statistics for a cloud of P Gaussians on the same device (after densify_and_prune changed P: the rows
@@ -170,6 +183,8 @@ class DensifyStats:
         self.grad_accum = torch.zeros(P, dtype=torch.float32, device=dev)
         self.denom = torch.zeros(P, dtype=torch.float32, device=dev)
         self.max_radii = torch.zeros(P, dtype=torch.int32, device=dev)
+        if self.abs_grad_accum is not None:
+            self.abs_grad_accum = torch.zeros(P, dtype=torch.float32, device=dev)
 
 
 _HELPED_FRAMES = [0]      # frames of this process whose binning stage reported look-back helps (hs_counters.reserved[4])
@@ -789,6 +804,13 @@ def _launch_backward(st: "_State", saved, gcol, ghdr, stages: int, want_pose: bo
         L.check(lib.hs_backward(C.byref(a), _stream()), "hs_backward")
         if to_stored is not None and stages == L.HS_BWD_ALL:
             to_stored(0, P)
+    # the AbsGS statistic (DensifyStats(absgrad=True)): one replay of the frame per call, whichever of the paths above ran,
+    # behind the render stage on this stream, under the gradients autograd handed over -- it reads what the render stage
+    # reads and nothing the backward writes
+    abs_accum = getattr(densify, "abs_grad_accum", None) if stages & L.HS_BWD_RENDER else None
+    if abs_accum is not None and stats is None and P > 0:
+        from . import importance as _imp
+        _imp._launch_abs_gradient(st, gcol, ghdr, galpha, ginvd, _imp._abs_target("DensifyStats", abs_accum, P, dev))
     return g
 
 

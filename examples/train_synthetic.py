@@ -16,6 +16,8 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --mcmc                 # learn the WHOLE cloud from a quarter of the points: MCMC policy
     python examples/train_synthetic.py --steps 300 --mcmc --filter-3d     # ... with the 3D smoothing filter of Mip-Splatting
     python examples/train_synthetic.py --steps 300 --topk                 # ... grown by score to a budget, pruned by contribution
+    python examples/train_synthetic.py --steps 200 --absgrad              # ... the published densify / prune on the AbsGS statistic
+    python examples/train_synthetic.py --steps 300 --topk --absgrad       # ... the budgeted policy, scored by the AbsGS statistic
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -37,6 +39,7 @@ from casualhdrsplat_amd import synthetic as S
 from casualhdrsplat_amd.importance import ContributionStats, accumulate_contributions
 from casualhdrsplat_amd.mcmc import grow, inject_noise, regularize, relocate
 from casualhdrsplat_amd.rows import densify_top_k, keep_top_k
+from casualhdrsplat_amd.densify import densify_and_prune
 from casualhdrsplat_amd.optim import cloud_param_groups
 from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.optim import GaussianAdam
@@ -67,7 +70,7 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
-        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False):
+        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False, absgrad=False):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -99,7 +102,15 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     gradient, under the factor schedule of mcmc -- the host knows the new size, nothing is read back.  At the last refinement,
     after the growth, a no_grad pass over all frames accumulates the blending-weight statistics
     (importance.accumulate_contributions) and rows.keep_top_k keeps the P - P // 10 rows with the largest maximum weight.  No
-    noise, no regularisers, no relocation.  Eager only; not together with mcmc.  The history gains P."""
+    noise, no regularisers, no relocation.  Eager only; not together with mcmc.  The history gains P.
+    absgrad: the statistics are a DensifyStats(absgrad=True) -- every backward also collects the absolute screen-gradient
+    statistic of AbsGS (importance.py).  With topk the score of densify_top_k is stats.mean_abs_grad() instead of
+    mean_grad(); on its own it is the same learner under the published policy, densify_and_prune(absgrad=True) every
+    `refine_every` steps while the cloud is below `cap_max` (default P), with the threshold AbsGS trainers use (twice the
+    default: magnitudes do not cancel).  Eager only; not together with mcmc."""
+    if absgrad and (mcmc or graph):
+        raise ValueError("absgrad=True (--absgrad) drives densify_and_prune or, with topk=True, densify_top_k: not together with "
+                         "mcmc=True (--mcmc) or graph=True (--graph)")
     if topk and mcmc:
         raise ValueError("topk=True (--topk) and mcmc=True (--mcmc) are two refinement policies for the same learner: choose one")
     if topk and graph:
@@ -112,7 +123,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     if mcmc and graph:
         raise ValueError("mcmc=True (--mcmc) is not supported together with graph=True (--graph): the number of Gaussians "
                          "changes at every refinement, a captured step is recorded for one size")
-    whole = mcmc or topk                # the learner does not know the cloud: all five stored tensors are leaves
+    scored = topk or absgrad            # its rasterizers collect a DensifyStats
+    whole = mcmc or scored              # the learner does not know the cloud: all five stored tensors are leaves
     if whole:
         fused_adam = raw = True
     if batch_frames and graph:
@@ -149,7 +161,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         def factory(settings):
             return GaussianRasterizer(settings, filter_3D=filt["filter_3D"], **how)
     score = {"stats": None, "keep_state": False, "last": None}     # --topk: the statistics its rasterizers collect
-    if topk:
+    if scored:
         def factory(settings):
             score["last"] = GaussianRasterizer(settings, densify_stats=None if score["keep_state"] else score["stats"],
                                                keep_state=score["keep_state"], **how)
@@ -188,8 +200,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         gen_dev = torch.Generator(device=dev).manual_seed(seed + 3)
         if filter_3d:
             filt["filter_3D"] = model.compute_filter_3D(cur["means3D"])
-        if topk:
-            score["stats"] = DensifyStats(P0, dev)
+        if scored:
+            score["stats"] = DensifyStats(P0, dev, absgrad=absgrad)
             extent = float(sc.means3D.std(dim=0).norm())
     elif fused_adam:
         opt = GaussianAdam([
@@ -284,7 +296,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             total += frames * (terms[0] + terms[1])
             if filter_3d:
                 extra["filter_len"] = int(filt["filter_3D"].shape[0])
-        if topk:
+        if scored:
             extra = dict(P=int(cur["means3D"].shape[0]))
         if it < steps:
             g0 = model.log_exposure.grad
@@ -308,7 +320,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                     P_now, left = int(cur["means3D"].shape[0]), len(refine_at) - refine_at.index(it)
                     factor = min(2.0, max(1.0, (cap / P_now) ** (1.0 / left) * (1.0 + 1e-12)))
                     k = min(cap - P_now, int(round(P_now * (factor - 1.0))))
-                    res = densify_top_k(opt, score["stats"].mean_grad(), k, extent=extent, generator=gen_dev)
+                    by = score["stats"].mean_abs_grad() if absgrad else score["stats"].mean_grad()
+                    res = densify_top_k(opt, by, k, extent=extent, generator=gen_dev)
                     score["stats"].resize(res.P_out)
                     if it == refine_at[-1]:                    # the final prune: by contribution, to nine tenths
                         cstats = ContributionStats(res.P_out, dev)
@@ -324,6 +337,14 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                         score["stats"].resize(res.P_out)
                     cur.update(res.params)
                     learn[:len(CLOUD)] = [cur[k] for k in CLOUD]
+            elif absgrad:
+                opt.step()
+                if it in refine_at and int(cur["means3D"].shape[0]) < cap:
+                    # (densify_and_prune zeroes the statistics at the new size itself)
+                    res = densify_and_prune(opt, score["stats"], extent=extent, grad_threshold=4e-4, absgrad=True,
+                                            generator=gen_dev)
+                    cur.update(res.params)
+                    learn[:len(CLOUD)] = [cur[k] for k in CLOUD]
             elif fused_adam:
                 opt.step(visibility=seen)
             else:
@@ -334,7 +355,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             print(f"step {it:4d}  {'L1' if lambda_dssim == 0 else 'loss'} {total / frames:.5f}  PSNR {ps / frames:6.2f} dB  |log dt - truth| {e_dt:.4f}  "
                   f"knot position error {e_pose:.5f}  ({(time.time() - t0) / max(it, 1) * 1e3:.1f} ms/step)" +
                   (f"  P {extra['P']}  regularisers {extra['reg_opacity']:.5f} + {extra['reg_scale']:.5f}" if mcmc else "") +
-                  (f"  P {extra['P']}" if topk else ""))
+                  (f"  P {extra['P']}" if scored else ""))
     out = dict(first=hist[0], last=hist[-1], history=hist)
     if whole:
         out["cloud"] = {k: cur[k].detach() for k in CLOUD}
@@ -377,6 +398,10 @@ def main(argv=None):
                          "densify_top_k clones / splits the rows with the largest mean view-space gradient towards --cap-max, and the "
                          "last refinement keeps the nine tenths with the largest blending weight (keep_top_k); eager only, not "
                          "with --mcmc")
+    ap.add_argument("--absgrad", action="store_true",
+                    help="collect the absolute screen-gradient statistic of AbsGS in every backward: with --topk it is the score "
+                         "of densify_top_k; on its own the same learner runs densify_and_prune(absgrad=True) every "
+                         "--refine-every steps while the cloud is below --cap-max; eager only, not with --mcmc")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
@@ -384,7 +409,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
-            refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk)
+            refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk,
+            absgrad=a.absgrad)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

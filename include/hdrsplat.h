@@ -978,6 +978,59 @@ typedef struct hs_contribution_args {
 HS_API int64_t hs_contribution_workspace_bytes(const hs_dims* dims);
 HS_API int hs_contribution(const hs_contribution_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Per-Gaussian absolute screen-gradient statistic (absgrad.hip): the refinement
+ * signal of AbsGS (gsplat's absgrad=True).  densify_grad_accum above holds |sum over pixels of ...|: the signed per-pixel
+ * terms of dL/dmean2D cancel across a large blurry Gaussian, which is the one that most needs splitting.  The terms exist
+ * only inside the backward's compositing loop, so this is a back-to-front replay of a finished hs_forward from the state it
+ * left in the three workspaces, under the upstream gradients hs_backward takes.  The threshold and the schedule stay with
+ * the trainer.
+ *
+ * Definition.  For one finished hs_forward call with n_poses poses in F = max(n_frames, 1) frames: take every pose k of frame
+ * f, every pixel p and every entry g that the published rule composites at (k, p) -- the decisions of hs_contribution's
+ * definition above.  Let w = dL/dG_{k,p,g} * G be the factor by which the backward multiplies dx = x_g - p_x and dy = y_g -
+ * p_y (G = e^power; dL is the upstream gradient with respect to pose k's radiance at p: the 1 / N of the pose average, the
+ * CRF chain through the stored radiance in either blur domain, dL_dout_hdr, the frame's exposure; dL_dout_alpha enters the
+ * background term, dL_dout_invdepth as a fourth channel -- all exactly as in hs_backward), and (A, B, C) the conic.  The
+ * per-pixel terms are
+ *     t_x = -(A dx + B dy) w * 0.5 W          t_y = -(C dy + B dx) w * 0.5 H
+ * -- the NDC-scaled units of dL_dmeans2D: the sum over p of t_x is the x entry hs_backward returns for that instance.  With
+ *     a_x[f,g] = sum over k in f (ascending) of sum over p of |t_x|          a_y likewise
+ * the call updates IN PLACE, frames ascending:  abs_grad_accum[g] += sqrt(a_x^2 + a_y^2)   (fp32).
+ * No normalisation beyond the 1 / N inside dL; the denominator a trainer divides by is densify_denom, which this call never
+ * touches.  A Gaussian with no term in a frame keeps its bits.  A call over F frames leaves, bit for bit, what F single-frame
+ * calls leave.  A call whose binning overflowed (hs_counters.overflow != 0) adds nothing -- decided on the device.
+ *
+ * Three kernels on the caller's stream, no atomics: the replay (one 8-byte record {sum |t_x|, sum |t_y|} per (tile,
+ * instance) pair at the pair's duplicateWithKeys slot), a fixed-order sum of every instance's contiguous slots, the fold over
+ * the poses of each frame.  The same inputs give the same bits.  The workspace is its own:
+ * hs_abs_gradient_workspace_bytes(dims) = align256(8 * capacity) + align256(8 * P * n_poses) (256 when that is 0), 256-byte
+ * aligned; every word is written before it is read.  The three state workspaces are only read.
+ * HS_EINVAL (reported before any HIP call): null args; dims that hs_plan refuses; dL_dout_alpha or dL_dout_invdepth with
+ * n_frames > 1; HS_FLAG_HDR without exposure, crf_table and dims.crf_K == crf_K; with P > 0 a null bg, geom, binning, image,
+ * ws, dL_dout_color or abs_grad_accum (workspaces 256-byte, arrays 4-byte aligned).  P == 0 is a successful no-op. */
+typedef struct hs_abs_gradient_args {
+    hs_dims dims;                 /* the dims of the hs_forward call */
+    int32_t flags;                /* the HS_FLAG_* of the call */
+    int32_t crf_K;
+    float crf_umin, crf_umax;
+    const float* bg;              /* [3] */
+    const float* exposure;        /* [F] (HDR) */
+    const float* crf_table;       /* [3,crf_K] (HDR) */
+    const void* geom;             /* state produced by hs_forward (same buffers), read only */
+    const void* binning;
+    const void* image;
+    void* ws;                     /* hs_abs_gradient_workspace_bytes(&dims) bytes, 256-byte aligned */
+    const float* dL_dout_color;   /* [F,3,H,W] */
+    const float* dL_dout_hdr;     /* [F,3,H,W] or NULL */
+    const float* dL_dout_alpha;   /* [H,W] or NULL */
+    const float* dL_dout_invdepth; /* [H,W] or NULL */
+    float* abs_grad_accum;        /* [P] */
+} hs_abs_gradient_args;
+
+/* a positive multiple of 256, non-decreasing in capacity and in P * n_poses; -1 (HS_EINVAL) for dims that hs_plan refuses */
+HS_API int64_t hs_abs_gradient_workspace_bytes(const hs_dims* dims);
+HS_API int hs_abs_gradient(const hs_abs_gradient_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
