@@ -10,11 +10,14 @@ relocation, growth, position noise and regularisers (mcmc.relocate, mcmc.grow, m
 3D smoothing filter of Mip-Splatting (smoothing.compute_filter_3D, GaussianRasterizer(..., filter_3D=...)), and the per-Gaussian
 blending-weight statistics contribution-based policies decide from (importance.accumulate_contributions), and the
 absolute screen-gradient statistic of AbsGS (DensifyStats(absgrad=True), importance.accumulate_abs_gradients), and the
-score-driven row edits that act on them (rows.prune_rows, rows.keep_top_k, rows.densify_top_k).  Compute lives in
+score-driven row edits that act on them (rows.prune_rows, rows.keep_top_k, rows.densify_top_k), and the per-frame
+bilateral-grid colour correction between the rasterizer's image and the loss (bilagrid.BilateralGrid, bilagrid.slice_image,
+bilagrid.tv_loss).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
 """
+from .bilagrid import BilateralGrid, slice_image, tv_loss
 from .densify import DensifyResult, densify_and_prune
 from .importance import ContributionStats, accumulate_abs_gradients, accumulate_contributions
 from .knn import knn_mean_dist2
@@ -31,5 +34,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats"
            "densify_and_prune", "DensifyResult", "knn_mean_dist2",
            "relocate", "grow", "inject_noise", "regularize", "RelocateResult", "GrowResult",
            "compute_filter_3D", "apply_filter_3D", "ContributionStats", "accumulate_contributions", "accumulate_abs_gradients",
-           "prune_rows", "keep_top_k", "densify_top_k", "RowsResult"]
+           "prune_rows", "keep_top_k", "densify_top_k", "RowsResult", "BilateralGrid", "slice_image", "tv_loss"]
 __version__ = "0.1.0"

@@ -200,6 +200,21 @@ class hs_abs_gradient_args(C.Structure):
                 ("abs_grad_accum", _fp)]
 
 
+class hs_bilagrid_args(C.Structure):
+    _fields_ = [("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("G", C.c_int32), ("L", C.c_int32), ("Y", C.c_int32),
+                ("X", C.c_int32), ("reserved", C.c_int32),
+                ("image", _fp), ("grids", _fp), ("grid_ids", _fp), ("out", _fp), ("dL_dout", _fp), ("dL_dimage", _fp),
+                ("dL_dgrids", _fp), ("workspace", _fp)]
+
+
+HS_BILAGRID_TV_WORKSPACE_BYTES = 24576
+
+
+class hs_bilagrid_tv_args(C.Structure):
+    _fields_ = [("G", C.c_int32), ("L", C.c_int32), ("Y", C.c_int32), ("X", C.c_int32),
+                ("grids", _fp), ("tv", _fp), ("dL_dtv", _fp), ("dL_dgrids", _fp), ("workspace", _fp)]
+
+
 def _call(args):
     """int f(const args*, void* hip_stream): the shape of most entry points"""
     return C.c_int, [C.POINTER(args), C.c_void_p]
@@ -251,6 +266,11 @@ SIGNATURES = {
     "hs_abs_gradient": _call(hs_abs_gradient_args),
     "hs_rows_workspace_bytes": (_i64, [_i64]),
     "hs_rows_plan": _call(hs_rows_args),
+    "hs_bilagrid_workspace_bytes": (_i64, [_i32] * 7),
+    "hs_bilagrid_slice": _call(hs_bilagrid_args),
+    "hs_bilagrid_slice_backward": _call(hs_bilagrid_args),
+    "hs_bilagrid_tv": _call(hs_bilagrid_tv_args),
+    "hs_bilagrid_tv_backward": _call(hs_bilagrid_tv_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

@@ -18,6 +18,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --topk                 # ... grown by score to a budget, pruned by contribution
     python examples/train_synthetic.py --steps 200 --absgrad              # ... the published densify / prune on the AbsGS statistic
     python examples/train_synthetic.py --steps 300 --topk --absgrad       # ... the budgeted policy, scored by the AbsGS statistic
+    python examples/train_synthetic.py --steps 300 --bilagrid             # vignetted, tinted observations; a bilateral grid per frame absorbs them
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -35,6 +36,7 @@ sys.path.insert(0, ROOT)
 import torch
 
 from casualhdrsplat_amd import scene_io
+from casualhdrsplat_amd.bilagrid import BilateralGrid
 from casualhdrsplat_amd import synthetic as S
 from casualhdrsplat_amd.importance import ContributionStats, accumulate_contributions
 from casualhdrsplat_amd.mcmc import grow, inject_noise, regularize, relocate
@@ -70,7 +72,8 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
-        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False, absgrad=False):
+        mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False, absgrad=False,
+        bilagrid=False, distort=None):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -107,7 +110,18 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     statistic of AbsGS (importance.py).  With topk the score of densify_top_k is stats.mean_abs_grad() instead of
     mean_grad(); on its own it is the same learner under the published policy, densify_and_prune(absgrad=True) every
     `refine_every` steps while the cloud is below `cap_max` (default P), with the threshold AbsGS trainers use (twice the
-    default: magnitudes do not cancel).  Eager only; not together with mcmc."""
+    default: magnitudes do not cancel).  Eager only; not together with mcmc.
+    bilagrid: the observations are multiplied by a smooth per-frame gain field (a vignette times a per-frame tint: what a phone
+    camera's white balance drift and lens do, and what no exposure scalar or response curve can express), and the learner
+    slices every frame's LDR image through its own bilateral grid (bilagrid.BilateralGrid(frames), identity at the start)
+    before the loss, adds 10 tv_loss() (gsplat's weight) to the step's loss and updates the grids with a torch.optim.Adam of
+    their own.  Works with every eager mode, with and without batch_frames; not with graph=True.  The history gains the
+    total variation, the reported loss includes its term, and the result the grids.  distort (default: as bilagrid) applies
+    the gain field on its own -- distort=True, bilagrid=False is the learner without the correction on the same observations."""
+    if bilagrid and graph:
+        raise ValueError("bilagrid=True (--bilagrid) is not supported together with graph=True (--graph): the captured step is "
+                         "built around the rasterizers' parameters alone (the grids have an optimizer of their own)")
+    distort = bilagrid if distort is None else distort
     if absgrad and (mcmc or graph):
         raise ValueError("absgrad=True (--absgrad) drives densify_and_prune or, with topk=True, densify_top_k: not together with "
                          "mcmc=True (--mcmc) or graph=True (--graph)")
@@ -149,6 +163,15 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         truth.trajectory.delta.copy_(0.004 * torch.randn(truth.trajectory.delta.shape, generator=gen))   # the true motion is not the prior
         cloud_true = {k: getattr(sc, k).to(dev) for k in CLOUD}
         targets = [truth(i, *[cloud_true[k] for k in CLOUD])[0] for i in range(frames)]
+        if distort:
+            # a vignette (1 at the centre, 0.65 in the corners) times one tint per frame and channel within +-15 %
+            gen_gain = torch.Generator().manual_seed(seed + 4)
+            yy = ((torch.arange(H) + 0.5) / H * 2 - 1)[:, None]
+            xx = ((torch.arange(W) + 0.5) / W * 2 - 1)[None, :]
+            vignette = 1.0 - 0.175 * (xx * xx + yy * yy)
+            for i in range(frames):
+                tint = 1.0 + 0.3 * (torch.rand(3, generator=gen_gain) - 0.5)
+                targets[i] = (targets[i] * (tint[:, None, None] * vignette[None]).to(dev)).clamp(0.0, 1.0)
 
     # the learner: the response curve is given, everything else starts off
     # --graph: one persistent sync-free rasterizer per captured frame, so that the step's gradient computation can be
@@ -222,6 +245,20 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     learn = [shs, raw_opac, model.log_exposure, model.trajectory.delta]
     if whole:
         learn = [cur[k] for k in CLOUD] + [model.log_exposure, model.trajectory.delta]
+    grid_tv = {"value": None}              # --bilagrid: the total variation of the step (a device scalar)
+    if bilagrid:
+        grids = BilateralGrid(frames, device=dev)
+        grid_opt = torch.optim.Adam(grids.parameters(), lr=2e-3, eps=1e-15)
+        grid_ids = torch.arange(frames, dtype=torch.int32, device=dev)
+        learn.append(grids.grids)
+
+    def backward_of(step_loss):
+        """backward of the step's loss, with gsplat's 10 tv(grids) added under --bilagrid"""
+        if bilagrid:
+            tv = grids.tv_loss()
+            grid_tv["value"] = tv.detach()
+            step_loss = step_loss + 10.0 * tv
+        step_loss.backward()
 
     def gradients():
         """Forward of every frame + backward of the summed loss; returns (per-frame losses, per-frame MSE) as tensors."""
@@ -234,6 +271,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         losses, mses = [], []
         for i in range(frames):
             ldr, _, radii, _ = model(i, cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"], cameras=cams)
+            if bilagrid:
+                ldr = grids(ldr, i)
             if fused_adam and not whole:   # (kernels only, written in place: the captured step leaves no copy node behind)
                 if i == 0:
                     torch.gt(radii, 0, out=seen)
@@ -244,7 +283,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             else:
                 losses.append(mean_by_rows((ldr - targets[i]).abs()))
             mses.append(mean_by_rows((ldr.detach() - targets[i]) ** 2))
-        torch.stack(losses).sum().backward()
+        backward_of(torch.stack(losses).sum())
         return torch.stack([l_.detach() for l_ in losses]), torch.stack(mses)
 
     target_batch = torch.stack(targets) if batch_frames else None
@@ -257,6 +296,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             p_.grad = None
         opac = cur["opacities"] if raw else torch.sigmoid(raw_opac)
         ldr, _, radii, _ = model.forward_frames(range(frames), cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"])
+        if bilagrid:
+            ldr = grids(ldr, grid_ids)
         if fused_adam and not whole:
             torch.gt(radii, 0, out=seen)      # (radii: the maximum over every frame's poses)
         if lambda_dssim > 0:
@@ -266,7 +307,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         else:
             losses = torch.stack([mean_by_rows((ldr[i] - targets[i]).abs()) for i in range(frames)])
         mses = torch.stack([mean_by_rows((ldr[i].detach() - targets[i]) ** 2) for i in range(frames)])
-        losses.sum().backward()
+        backward_of(losses.sum())
         return losses.detach(), mses
 
     step_fn = gradients_batched if batch_frames else gradients
@@ -298,7 +339,12 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                 extra["filter_len"] = int(filt["filter_3D"].shape[0])
         if scored:
             extra = dict(P=int(cur["means3D"].shape[0]))
+        if bilagrid:
+            extra["tv"] = float(grid_tv["value"])
+            total += frames * 10.0 * extra["tv"]
         if it < steps:
+            if bilagrid:
+                grid_opt.step()
             g0 = model.log_exposure.grad
             if g0 is not None:
                 g0[0] = 0.0                                    # frame 0's exposure is the gauge
@@ -357,6 +403,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                   (f"  P {extra['P']}  regularisers {extra['reg_opacity']:.5f} + {extra['reg_scale']:.5f}" if mcmc else "") +
                   (f"  P {extra['P']}" if scored else ""))
     out = dict(first=hist[0], last=hist[-1], history=hist)
+    if bilagrid:
+        out["grids"] = grids.grids.detach()
     if whole:
         out["cloud"] = {k: cur[k].detach() for k in CLOUD}
         if filter_3d:
@@ -402,6 +450,10 @@ def main(argv=None):
                     help="collect the absolute screen-gradient statistic of AbsGS in every backward: with --topk it is the score "
                          "of densify_top_k; on its own the same learner runs densify_and_prune(absgrad=True) every "
                          "--refine-every steps while the cloud is below --cap-max; eager only, not with --mcmc")
+    ap.add_argument("--bilagrid", action="store_true",
+                    help="multiply the observations by a smooth per-frame gain field (vignette x tint) and slice every frame's image "
+                         "through its own bilateral grid before the loss (+ 10 tv_loss(), the grids under torch.optim.Adam); "
+                         "eager only (not with --graph)")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
@@ -410,7 +462,7 @@ def main(argv=None):
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
             refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk,
-            absgrad=a.absgrad)
+            absgrad=a.absgrad, bilagrid=a.bilagrid)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")

@@ -1031,6 +1031,68 @@ typedef struct hs_abs_gradient_args {
 HS_API int64_t hs_abs_gradient_workspace_bytes(const hs_dims* dims);
 HS_API int hs_abs_gradient(const hs_abs_gradient_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Bilateral-grid image correction ("Bilateral Guided Radiance Field Processing",
+ * SIGGRAPH 2024), fused (bilagrid.hip): every frame owns a small 3-D lattice of 3 x 4 affine colour matrices addressed by pixel
+ * position and luma; the rendered image is sliced through it between the rasterizer and the loss, and a total-variation term
+ * keeps the lattice smooth.
+ *
+ * Shapes.  grids [G, 12, L, Y, X] fp32: coefficient c = 4 i + k is entry (row i, column k) of the matrix, the identity has
+ * c = 0, 5, 10 equal to 1.  Images [F, 3, H, W] fp32 planar (the rasterizer's output).  grid_ids int32 [F] IN DEVICE MEMORY.
+ * Axis rule, for an axis of n lattice points and a value v: n == 1: i0 = i1 = 0, f = 0; else t = min(max(v, 0), 1) (n - 1),
+ * i0 = min(floor(t), n - 2), i1 = i0 + 1, f = t - i0 (a NaN v counts as 0).
+ * Forward, per pixel (px, py) of frame fr with colour (r, g, b): x = (px + 0.5) / W on X, y = (py + 0.5) / H on Y,
+ * z = 0.299 r + 0.587 g + 0.114 b on L; A[c] = the sum over the eight corners of w_x w_y w_z grids[grid_ids[fr], c, l, yy, xx]
+ * (1 - f at the i0 side, f at the i1 side); out_i = A[4i] r + A[4i+1] g + A[4i+2] b + A[4i+3].  This is grid_sample(grids,
+ * 2 (x, y, z) - 1, bilinear, padding border, align_corners) followed by the affine.  The fp32 operation ORDER is stated at
+ * the top of bilagrid.hip and restated by tests/bilagrid_reference.py: forward and dL_dimage are compared bit for bit.
+ * A frame whose id is outside [0, G) (-1: "no grid", an evaluation view) is the identity: out is bit for bit image, dL_dimage
+ * bit for bit dL_dout, and the frame adds nothing to dL_dgrids.
+ * Backward.  dL_dgrids[g, c = 4i + k, l, yy, xx] = the sum, over the frames with grid_ids[fr] == g in ascending fr and their
+ * pixels, of w_x w_y w_z dL_dout_i v_k, v = (r, g, b, 1) -- a gather per destination in a fixed order, no atomics: the same
+ * inputs give the same bits.  EVERY element is written, by a kernel; a grid no frame used gets exact zeros.
+ * dL_dimage_k = sum_i A[4i+k] dL_dout_i, plus, where 0 < z < 1 strictly and L > 1, luma_k (L - 1) sum_i dL_dout_i
+ * sum_k' (dA[4i+k'] / df_z) v_k'.  The pixel position carries no gradient.
+ * Limits (HS_EINVAL): F, H, W, G >= 1, 1 <= L <= 16, 1 <= X, Y <= 64, 3 F H W < 2^31, 12 G L Y X < 2^31; float and id
+ * pointers 4-byte aligned, the workspace 256-byte aligned.  The caller owns every byte, nothing is allocated, the work is
+ * enqueued on the caller's stream, nothing synchronises, and no word of the workspace is read before it is written. */
+typedef struct hs_bilagrid_args {
+    int32_t F, H, W, G, L, Y, X;
+    int32_t reserved;
+    const float* image;           /* [F, 3, H, W] */
+    const float* grids;           /* [G, 12, L, Y, X] */
+    const int32_t* grid_ids;      /* [F], device memory */
+    float* out;                   /* [F, 3, H, W] written by hs_bilagrid_slice */
+    const float* dL_dout;         /* [F, 3, H, W] (backward) */
+    float* dL_dimage;             /* [F, 3, H, W] written by the backward, or NULL: skipped */
+    float* dL_dgrids;             /* [G, 12, L, Y, X] written by the backward, or NULL: skipped */
+    void* workspace;              /* hs_bilagrid_workspace_bytes(...) bytes; only read / written when dL_dgrids != NULL */
+} hs_bilagrid_args;
+
+/* align256(4 F chunks 12 L Y X): one record of the 12 L sums of every lattice column per frame and chunk of 32 rows of the
+ * column's pixel footprint.  chunks = ceil(tallest / 32), tallest = the most rows hi - lo + 1 any lattice row yy has, with
+ * (Y == 1: lo = 0, hi = H - 1)  m = 2 + H / 2^20, lo = max(0, yy == 0 ? 0 : floor((yy - 1) H / (Y - 1)) - m),
+ * hi = min(H - 1, ceil((yy + 1) H / (Y - 1)) + m).  -1 (HS_EINVAL) outside the limits above. */
+HS_API int64_t hs_bilagrid_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t G, int32_t L, int32_t Y, int32_t X);
+HS_API int hs_bilagrid_slice(const hs_bilagrid_args* args, void* hip_stream);
+HS_API int hs_bilagrid_slice_backward(const hs_bilagrid_args* args, void* hip_stream);
+
+/* Total variation of the grids: over the three lattice axes of size > 1, the mean over all grids, coefficients and positions
+ * of (grids[.., j + 1] - grids[.., j])^2 along that axis; an axis of size 1 adds nothing.  Differences and sums in fp64, the
+ * blocks added in a fixed order: the same bits on every run.  The backward writes dL_dgrids = dL_dtv[0] * d tv / d grids
+ * (every element; dL_dtv is read on the device).  Limits: those of the lattice above. */
+#define HS_BILAGRID_TV_WORKSPACE_BYTES 24576 /* 1024 blocks x 3 fp64 sums */
+typedef struct hs_bilagrid_tv_args {
+    int32_t G, L, Y, X;
+    const float* grids;           /* [G, 12, L, Y, X] */
+    float* tv;                    /* [1] written by hs_bilagrid_tv */
+    const float* dL_dtv;          /* [1] upstream gradient (backward) */
+    float* dL_dgrids;             /* [G, 12, L, Y, X] written by the backward */
+    void* workspace;              /* HS_BILAGRID_TV_WORKSPACE_BYTES bytes, 256-byte aligned (forward only) */
+} hs_bilagrid_tv_args;
+
+HS_API int hs_bilagrid_tv(const hs_bilagrid_tv_args* args, void* hip_stream);
+HS_API int hs_bilagrid_tv_backward(const hs_bilagrid_tv_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
