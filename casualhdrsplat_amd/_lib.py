@@ -215,6 +215,12 @@ class hs_bilagrid_tv_args(C.Structure):
                 ("grids", _fp), ("tv", _fp), ("dL_dtv", _fp), ("dL_dgrids", _fp), ("workspace", _fp)]
 
 
+class hs_vq_args(C.Structure):
+    _fields_ = [("N", C.c_int32), ("D", C.c_int32), ("K", C.c_int32),
+                ("x", _fp), ("weights", _fp), ("codebook_in", _fp), ("codes", _fp), ("dist2", _fp), ("codebook_out", _fp),
+                ("counts", _fp), ("workspace", _fp)]
+
+
 def _call(args):
     """int f(const args*, void* hip_stream): the shape of most entry points"""
     return C.c_int, [C.POINTER(args), C.c_void_p]
@@ -271,6 +277,9 @@ SIGNATURES = {
     "hs_bilagrid_slice_backward": _call(hs_bilagrid_args),
     "hs_bilagrid_tv": _call(hs_bilagrid_tv_args),
     "hs_bilagrid_tv_backward": _call(hs_bilagrid_tv_args),
+    "hs_vq_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "hs_vq_assign": _call(hs_vq_args),
+    "hs_vq_update": _call(hs_vq_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

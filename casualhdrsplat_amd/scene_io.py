@@ -168,6 +168,46 @@ def load_ply(path: str) -> GaussianCloud:
                          t(col("rot_0", "rot_1", "rot_2", "rot_3")))
 
 
+VQ_VERSION = 1
+
+
+def save_vq(path: str, cloud: GaussianCloud, sh_codebook: torch.Tensor, sh_codes: torch.Tensor) -> None:
+    """The cloud with its view-dependent SH coefficients replaced by codes into a shared codebook (vq.quantize_sh), as an
+    uncompressed .npz written to exactly `path`: `version`; means3D [P,3], sh_dc [P,1,3], opacity_logit [P,1], log_scales [P,3],
+    rotations [P,4] as little-endian fp32 with the bits they have; sh_codebook [K,M-1,3] fp32; sh_codes [P] as uint16.
+    cloud.shs[:, 1:] is not written (only its DC term is): load_vq rebuilds it as sh_codebook[sh_codes]."""
+    def f32(t):
+        return np.ascontiguousarray(t.detach().cpu().numpy(), dtype="<f4")
+    P = cloud.means3D.shape[0]
+    book = f32(sh_codebook)
+    codes = sh_codes.detach().cpu().numpy()
+    if book.ndim != 3 or book.shape[2] != 3 or not (1 <= book.shape[0] <= 65536):
+        raise ValueError(f"save_vq: sh_codebook must be [K <= 65536, M-1, 3], got {book.shape}")
+    if book.shape[1] != cloud.shs.shape[1] - 1:
+        raise ValueError(f"save_vq: sh_codebook holds {book.shape[1]} coefficients per entry, the cloud has {cloud.shs.shape[1]} - 1")
+    if codes.shape != (P,) or codes.dtype.kind not in "iu":
+        raise ValueError(f"save_vq: sh_codes must hold one integer code per Gaussian ({P}), got {codes.dtype} {codes.shape}")
+    if P and (codes.min() < 0 or codes.max() >= book.shape[0]):
+        raise ValueError(f"save_vq: sh_codes outside [0, {book.shape[0]})")
+    with open(path, "wb") as f:
+        np.savez(f, version=np.int32(VQ_VERSION), means3D=f32(cloud.means3D), sh_dc=f32(cloud.shs[:, :1, :]),
+                 opacity_logit=f32(cloud.opacity_logit), log_scales=f32(cloud.log_scales), rotations=f32(cloud.rotations),
+                 sh_codebook=book, sh_codes=codes.astype("<u2"))
+
+
+def load_vq(path: str) -> GaussianCloud:
+    """The cloud save_vq wrote, with shs = [sh_dc, sh_codebook[sh_codes]]."""
+    with np.load(path) as z:
+        if int(z["version"]) != VQ_VERSION:
+            raise ValueError(f"{path}: version {int(z['version'])}, this reader knows {VQ_VERSION}")
+        book, codes = z["sh_codebook"], z["sh_codes"].astype(np.int64)
+        if codes.size and codes.max() >= book.shape[0]:
+            raise ValueError(f"{path}: a code outside the {book.shape[0]} codebook entries")
+        shs = np.concatenate([z["sh_dc"], book[codes]], axis=1).astype(np.float32)
+        t = lambda name: torch.from_numpy(z[name].astype(np.float32))
+        return GaussianCloud(t("means3D"), torch.from_numpy(shs), t("opacity_logit"), t("log_scales"), t("rotations"))
+
+
 # ------------------------------------------------------------------------------------------- COLMAP sparse models
 _CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5),
                   4: ("OPENCV", 8), 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5),

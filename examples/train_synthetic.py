@@ -19,6 +19,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 200 --absgrad              # ... the published densify / prune on the AbsGS statistic
     python examples/train_synthetic.py --steps 300 --topk --absgrad       # ... the budgeted policy, scored by the AbsGS statistic
     python examples/train_synthetic.py --steps 300 --bilagrid             # vignetted, tinted observations; a bilateral grid per frame absorbs them
+    python examples/train_synthetic.py --steps 300 --topk --vq 1024       # ... then the SH coefficients as 16-bit codes into a k-means codebook
 
 Gauge: exposure x radiance x response is determined only up to a common factor, so the response curve and the first frame's
 exposure are held at their true values (a real capture pins them with EXIF exposure ratios or a calibrated response).
@@ -28,6 +29,7 @@ import functools
 import math
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,6 +49,7 @@ from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.optim import GaussianAdam
 from casualhdrsplat_amd.graphs import GraphedStep
 from casualhdrsplat_amd.rasterizer import DensifyStats, GaussianRasterizer
+from casualhdrsplat_amd.vq import dequantize_sh, quantize_sh
 from casualhdrsplat_amd.image_formation import (FrameRasterizers, HDRBlurFormation, ImplicitCRF, TrajectorySpline,
                                                   knots_from_lookat)
 
@@ -73,7 +76,7 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
         mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False, absgrad=False,
-        bilagrid=False, distort=None):
+        bilagrid=False, distort=None, vq=0):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -117,7 +120,14 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     before the loss, adds 10 tv_loss() (gsplat's weight) to the step's loss and updates the grids with a torch.optim.Adam of
     their own.  Works with every eager mode, with and without batch_frames; not with graph=True.  The history gains the
     total variation, the reported loss includes its term, and the result the grids.  distort (default: as bilagrid) applies
-    the gain field on its own -- distort=True, bilagrid=False is the learner without the correction on the same observations."""
+    the gain field on its own -- distort=True, bilagrid=False is the learner without the correction on the same observations.
+    vq = K > 0 (needs deg >= 1): after the last step the cloud's view-dependent SH coefficients are quantised to K centroids
+    (vq.quantize_sh, 10 iterations) -- weighted by the blending-weight sums of a pass over all frames
+    (ContributionStats.weight_sum) where the learner's rasterizers keep the state that pass needs (topk, absgrad), unweighted
+    otherwise --, every frame is rendered again from the dequantised cloud, and the result gains `vq`: the PSNR between the
+    two renders and the sizes of the cloud as scene_io.save_ply and as scene_io.save_vq write it."""
+    if vq and deg < 1:
+        raise ValueError("vq=K (--vq K) needs deg >= 1 (--deg): a degree-0 cloud has no view-dependent coefficients to quantise")
     if bilagrid and graph:
         raise ValueError("bilagrid=True (--bilagrid) is not supported together with graph=True (--graph): the captured step is "
                          "built around the rasterizers' parameters alone (the grids have an optimizer of their own)")
@@ -321,6 +331,18 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                 p_.grad = g_
             return out
 
+    def contributions(q):
+        """The blending-weight statistics of the cloud `q` over all frames (scored learners: their rasterizers can keep the state)"""
+        cstats = ContributionStats(int(q["means3D"].shape[0]), dev)
+        score["keep_state"] = True
+        with torch.no_grad():
+            cams = model.cameras_all()
+            for i in range(frames):
+                model(i, q["means3D"], q["opacities"], q["shs"], q["scales"], q["rotations"], cameras=cams)
+                accumulate_contributions(score["last"], cstats)
+        score["keep_state"] = False
+        return cstats
+
     hist = []
     t0 = time.time()
     for it in range(steps + 1):
@@ -370,16 +392,7 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                     res = densify_top_k(opt, by, k, extent=extent, generator=gen_dev)
                     score["stats"].resize(res.P_out)
                     if it == refine_at[-1]:                    # the final prune: by contribution, to nine tenths
-                        cstats = ContributionStats(res.P_out, dev)
-                        score["keep_state"] = True
-                        with torch.no_grad():
-                            cams = model.cameras_all()
-                            q = res.params
-                            for i in range(frames):
-                                model(i, q["means3D"], q["opacities"], q["shs"], q["scales"], q["rotations"], cameras=cams)
-                                accumulate_contributions(score["last"], cstats)
-                        score["keep_state"] = False
-                        res = keep_top_k(opt, cstats.weight_max, res.P_out - res.P_out // 10)
+                        res = keep_top_k(opt, contributions(res.params).weight_max, res.P_out - res.P_out // 10)
                         score["stats"].resize(res.P_out)
                     cur.update(res.params)
                     learn[:len(CLOUD)] = [cur[k] for k in CLOUD]
@@ -403,6 +416,28 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                   (f"  P {extra['P']}  regularisers {extra['reg_opacity']:.5f} + {extra['reg_scale']:.5f}" if mcmc else "") +
                   (f"  P {extra['P']}" if scored else ""))
     out = dict(first=hist[0], last=hist[-1], history=hist)
+    if vq:
+        with torch.no_grad():
+            q = {k: v.detach() for k, v in cur.items()}
+            weights = contributions(q).weight_sum if scored else None
+            book, codes = quantize_sh(q["shs"], vq, iters=10, weights=weights, generator=torch.Generator().manual_seed(seed + 5))
+            shs_q = dequantize_sh(q["shs"][:, :1].contiguous(), book, codes)
+            cams = model.cameras_all()
+            opac = q["opacities"] if raw else torch.sigmoid(q["opacities"])
+            mse = []
+            for i in range(frames):
+                full = model(i, q["means3D"], opac, q["shs"], q["scales"], q["rotations"], cameras=cams)[0]
+                quant = model(i, q["means3D"], opac, shs_q, q["scales"], q["rotations"], cameras=cams)[0]
+                mse.append(mean_by_rows((full - quant) ** 2))
+            psnr = float((-10.0 * torch.log10(torch.stack(mse).clamp_min(1e-12))).mean())
+            stored = scene_io.GaussianCloud(q["means3D"], q["shs"], q["opacities"], q["scales"] if raw else q["scales"].log(),
+                                            q["rotations"])
+            with tempfile.TemporaryDirectory() as tmp:
+                scene_io.save_ply(os.path.join(tmp, "cloud.ply"), stored)
+                scene_io.save_vq(os.path.join(tmp, "cloud.npz"), stored, book, codes)
+                sizes = [os.path.getsize(os.path.join(tmp, n)) for n in ("cloud.ply", "cloud.npz")]
+        out["vq"] = dict(K=int(vq), P=int(q["means3D"].shape[0]), weighted=weights is not None, psnr_full_vs_quantised_db=psnr,
+                         ply_bytes=sizes[0], vq_bytes=sizes[1], sh_codebook=book, sh_codes=codes)
     if bilagrid:
         out["grids"] = grids.grids.detach()
     if whole:
@@ -454,6 +489,10 @@ def main(argv=None):
                     help="multiply the observations by a smooth per-frame gain field (vignette x tint) and slice every frame's image "
                          "through its own bilateral grid before the loss (+ 10 tv_loss(), the grids under torch.optim.Adam); "
                          "eager only (not with --graph)")
+    ap.add_argument("--vq", type=int, default=0, metavar="K",
+                    help="after training, quantise the view-dependent SH coefficients to K centroids (needs --deg >= 1; weighted by "
+                         "the blending-weight sums under --topk / --absgrad), render every frame again from the dequantised cloud and "
+                         "print the PSNR between the two renders and both file sizes")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
@@ -462,10 +501,15 @@ def main(argv=None):
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
             refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk,
-            absgrad=a.absgrad, bilagrid=a.bilagrid)
+            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")
+    if a.vq:
+        v = r["vq"]
+        print(f"vq K {v['K']} ({'weighted by contribution' if v['weighted'] else 'unweighted'}), P {v['P']}: PSNR full vs quantised "
+              f"{v['psnr_full_vs_quantised_db']:.2f} dB; save_ply {v['ply_bytes']} B, save_vq {v['vq_bytes']} B "
+              f"({v['ply_bytes'] / v['vq_bytes']:.2f} x)")
 
 
 if __name__ == "__main__":

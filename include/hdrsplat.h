@@ -1093,6 +1093,43 @@ typedef struct hs_bilagrid_tv_args {
 HS_API int hs_bilagrid_tv(const hs_bilagrid_tv_args* args, void* hip_stream);
 HS_API int hs_bilagrid_tv_backward(const hs_bilagrid_tv_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) k-means vector quantisation of the rows of a matrix (vq.hip): the codebook compression
+ * of a finished cloud's view-dependent SH coefficients (LightGaussian's VecTree step, gsplat's PngCompression on shN,
+ * Compact3D).  Lloyd's two steps; the loop, the initialisation and what is quantised are the caller's.
+ *
+ * Assign.  x [N, D] fp32 row-major, codebook_in [K, D] fp32.  d2(i, k): acc = 0; for d ascending: t = x[i,d] - c[k,d],
+ * acc = acc + t * t -- fp32, every operation rounded once, no contraction.  codes[i] = the k of the smallest d2, scanning k
+ * ascending with a strict < against a running best that starts at +inf: ties go to the lower k; a row whose distances are all
+ * NaN gets code 0 and dist2 = +inf.  dist2[i] = the winning value.  tests/vq_reference.py restates it; compared bit for bit.
+ * Update.  For each cluster k: S_w = sum of (double)weights[i] over its members (weights NULL: all 1), S_d = sum of
+ * (double)weights[i] (double)x[i,d]; codebook_out[k,d] = (float)(S_d / S_w) when S_w > 0, else codebook_in[k,d] bit for bit (an
+ * empty cluster, or one whose weights are all zero); counts[k] = the members of k whatever their weights.  A code outside
+ * [0, K) belongs to no cluster.  Negative weights are undefined; nothing reads them on the host.  The fp64 sums are added in a
+ * fixed order that depends on (N, K, codes) alone -- the top of vq.hip states it -- with no atomics: the same inputs give
+ * the same bits, whatever the workspace held.  codebook_out must not alias codebook_in.
+ * Limits (HS_EINVAL, before any HIP call): 0 <= N <= 2^30, 1 <= D <= 48, 1 <= K <= 65536; pointers 4-byte aligned, the
+ * workspace 256-byte aligned; N = 0 is valid (assign writes nothing; update copies codebook_in and zeroes counts; x, codes and
+ * the workspace may then be NULL).  The caller owns every byte, nothing is allocated, the work is enqueued on the caller's
+ * stream and nothing synchronises. */
+typedef struct hs_vq_args {
+    int32_t N, D, K;
+    const float* x;               /* [N, D] */
+    const float* weights;         /* [N] >= 0, or NULL: all 1 (update) */
+    const float* codebook_in;     /* [K, D] */
+    int32_t* codes;               /* [N]: written by the assignment, read by the update */
+    float* dist2;                 /* [N] written by the assignment, or NULL: skipped */
+    float* codebook_out;          /* [K, D] written by the update */
+    int32_t* counts;              /* [K] written by the update */
+    void* workspace;              /* hs_vq_workspace_bytes(N, D, K) bytes (update only) */
+} hs_vq_args;
+
+/* a positive multiple of 256, non-decreasing in N; -1 (HS_EINVAL) outside the limits above.  No HIP call. */
+HS_API int64_t hs_vq_workspace_bytes(int32_t N, int32_t D, int32_t K);
+/* reads x, codebook_in; writes codes, dist2 (may be NULL) */
+HS_API int hs_vq_assign(const hs_vq_args* args, void* hip_stream);
+/* reads x, weights (may be NULL), codes, codebook_in; writes codebook_out, counts */
+HS_API int hs_vq_update(const hs_vq_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
