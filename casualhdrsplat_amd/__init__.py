@@ -13,7 +13,8 @@ absolute screen-gradient statistic of AbsGS (DensifyStats(absgrad=True), importa
 score-driven row edits that act on them (rows.prune_rows, rows.keep_top_k, rows.densify_top_k), and the per-frame
 bilateral-grid colour correction between the rasterizer's image and the loss (bilagrid.BilateralGrid, bilagrid.slice_image,
 bilagrid.tv_loss), and the k-means codebook compression of a finished cloud's view-dependent SH coefficients (vq.quantize_sh,
-vq.kmeans, scene_io.save_vq).  Compute lives in
+vq.kmeans, scene_io.save_vq), and the lens undistortion of captured frames, fused with the downscale to the training resolution
+(undistort.undistort_map, undistort.undistort_frames, undistort.undistorted_camera).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
@@ -29,6 +30,7 @@ from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSet
                          SortChainStalled, inspect_state, rasterize_gaussians)
 from .rows import RowsResult, densify_top_k, keep_top_k, prune_rows
 from .smoothing import apply_filter_3D, compute_filter_3D
+from .undistort import UndistortMap, undistort_frames, undistort_map, undistorted_camera
 from .vq import VQResult, dequantize_sh, kmeans, kmeans_assign, kmeans_update, quantize_sh
 
 __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats", "BinningOverflow", "SortChainStalled",
@@ -37,5 +39,6 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats"
            "relocate", "grow", "inject_noise", "regularize", "RelocateResult", "GrowResult",
            "compute_filter_3D", "apply_filter_3D", "ContributionStats", "accumulate_contributions", "accumulate_abs_gradients",
            "prune_rows", "keep_top_k", "densify_top_k", "RowsResult", "BilateralGrid", "slice_image", "tv_loss",
-           "kmeans", "kmeans_assign", "kmeans_update", "quantize_sh", "dequantize_sh", "VQResult"]
+           "kmeans", "kmeans_assign", "kmeans_update", "quantize_sh", "dequantize_sh", "VQResult",
+           "undistorted_camera", "undistort_map", "undistort_frames", "UndistortMap"]
 __version__ = "0.1.0"

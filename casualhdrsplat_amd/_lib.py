@@ -221,6 +221,16 @@ class hs_vq_args(C.Structure):
                 ("counts", _fp), ("workspace", _fp)]
 
 
+HS_CAMERA_MODELS = ("SIMPLE_PINHOLE", "PINHOLE", "SIMPLE_RADIAL", "RADIAL", "OPENCV", "OPENCV_FISHEYE", "FULL_OPENCV")  # HS_CAMERA_* = index
+
+
+class hs_undistort_args(C.Structure):
+    _fields_ = [("model", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("Wf", C.c_int32), ("Hf", C.c_int32), ("F", C.c_int32),
+                ("factor", C.c_int32), ("frames_u8", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float), ("k", C.c_float * 8),
+                ("map", _fp), ("valid", _fp), ("frames", _fp), ("out", _fp)]
+
+
 def _call(args):
     """int f(const args*, void* hip_stream): the shape of most entry points"""
     return C.c_int, [C.POINTER(args), C.c_void_p]
@@ -280,6 +290,8 @@ SIGNATURES = {
     "hs_vq_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "hs_vq_assign": _call(hs_vq_args),
     "hs_vq_update": _call(hs_vq_args),
+    "hs_undistort_map": _call(hs_undistort_args),
+    "hs_undistort_remap": _call(hs_undistort_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

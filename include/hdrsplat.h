@@ -1130,6 +1130,62 @@ HS_API int hs_vq_assign(const hs_vq_args* args, void* hip_stream);
 /* reads x, weights (may be NULL), codes, codebook_in; writes codebook_out, counts */
 HS_API int hs_vq_update(const hs_vq_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Lens undistortion of captured frames, fused with the area-filtered downscale to the
+ * training resolution (undistort.hip): the step between a COLMAP camera with distortion and the pinhole rasterizer.  One map
+ * per camera (hs_undistort_map), then every frame of that camera through it (hs_undistort_remap).
+ *
+ * Cameras.  model = COLMAP's model id (HS_CAMERA_*); fx, fy, cx, cy and k[8] are the source camera's parameters rounded to
+ * fp32 by the host, k in COLMAP's order after the intrinsics (SIMPLE_RADIAL: k; RADIAL: k1 k2; OPENCV: k1 k2 p1 p2;
+ * FULL_OPENCV: k1 k2 p1 p2 k3 k4 k5 k6; OPENCV_FISHEYE: k1 k2 k3 k4; unused entries are ignored).  Pixel coordinates are
+ * COLMAP's: the centre of pixel (i, j) is at (i + 0.5, j + 0.5).
+ * Map.  The undistorted full-resolution grid is Wf x Hf with the source's fx, fy and its principal point at (Wf / 2, Hf / 2).
+ * For its pixel (x, y): u = ((x + 0.5) - Wf / 2) / fx, v = ((y + 0.5) - Hf / 2) / fy; (ud, vd) = the model's forward mapping
+ * of (u, v); map[y, x] = (sx, sy) = (ud * fx + cx, vd * fy + cy); valid[y, x] = 1 when 0.5 <= sx <= W - 0.5 and
+ * 0.5 <= sy <= H - 0.5, else 0 (a NaN gives 0).  All in fp32, every operation rounded once, in the order stated at the top of
+ * undistort.hip and restated by tests/undistort_reference.py: compared bit for bit (OPENCV_FISHEYE calls the library atanf
+ * and is compared in pixels instead).
+ * Remap.  frames: uint8 [F, H, W, 3] (frames_u8 != 0; what a decoder delivers) or fp32 [F, 3, H, W]; factor S in {1, 2, 3, 4,
+ * 8}, Wf and Hf multiples of S; out fp32 [F, 3, Hf / S, Wf / S].  out[f, c, yo, xo] = the sum, over j = 0 .. S-1 and inside
+ * that i = 0 .. S-1 ascending and starting from 0, of the bilinear sample of channel c of frame f at map[yo S + j, xo S + i],
+ * divided by (float)(S S), and for uint8 frames then divided by 255.  Bilinear sample at (sx, sy): a NaN coordinate samples as
+ * 0; px = min(max(sx - 0.5, 0), W - 1), x0 = min((int)floor(px), W - 2), wx = px - x0, likewise py, y0, wy with H;
+ * top = (1 - wx) t00 + wx t01, bottom = (1 - wx) t10 + wx t11, sample = (1 - wy) top + wy bottom, t_ab = the tap at
+ * (x0 + b, y0 + a): exact on every pixel centre.  EVERY element of map / valid / out is written, by a kernel, whatever the
+ * buffers held.  No atomics.
+ * Limits (HS_EINVAL, reported before any HIP call): args non-null; model one of the seven HS_CAMERA_* below; 2 <= W, H <=
+ * 16384; 0 <= Wf, Hf <= 16384; remap: factor in {1, 2, 3, 4, 8} dividing Wf and Hf, F >= 0, 3 F H W < 2^31 and
+ * 3 F (Hf / S) (Wf / S) < 2^31; map: fx, fy finite and > 0, cx, cy and k finite.  Pointers: map non-null and 8-byte aligned,
+ * valid non-null (map), frames non-null and 4-byte aligned when fp32, out non-null and 4-byte aligned (remap) -- except that
+ * F = 0 or an empty grid (Wf = 0 or Hf = 0) is a valid call that launches nothing and returns HS_OK, with or without
+ * pointers (those given must still be aligned).  The caller owns every byte, nothing is allocated, the work is enqueued on
+ * the caller's stream and nothing synchronises. */
+#define HS_CAMERA_SIMPLE_PINHOLE 0
+#define HS_CAMERA_PINHOLE 1
+#define HS_CAMERA_SIMPLE_RADIAL 2
+#define HS_CAMERA_RADIAL 3
+#define HS_CAMERA_OPENCV 4
+#define HS_CAMERA_OPENCV_FISHEYE 5
+#define HS_CAMERA_FULL_OPENCV 6
+typedef struct hs_undistort_args {
+    int32_t model;                /* HS_CAMERA_* (map) */
+    int32_t W, H;                 /* source frame */
+    int32_t Wf, Hf;               /* undistorted full-resolution grid = the map */
+    int32_t F;                    /* frames (remap) */
+    int32_t factor;               /* S (remap) */
+    int32_t frames_u8;            /* != 0: frames are uint8 [F, H, W, 3]; 0: fp32 [F, 3, H, W] (remap) */
+    float fx, fy, cx, cy;         /* source intrinsics (map) */
+    float k[8];                   /* distortion coefficients (map) */
+    float* map;                   /* [Hf, Wf, 2]: written by hs_undistort_map, read by hs_undistort_remap */
+    uint8_t* valid;               /* [Hf, Wf] written by hs_undistort_map */
+    const void* frames;           /* (remap) */
+    float* out;                   /* [F, 3, Hf / S, Wf / S] written by hs_undistort_remap */
+} hs_undistort_args;
+
+/* reads the camera; writes map, valid */
+HS_API int hs_undistort_map(const hs_undistort_args* args, void* hip_stream);
+/* reads map, frames; writes out */
+HS_API int hs_undistort_remap(const hs_undistort_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
