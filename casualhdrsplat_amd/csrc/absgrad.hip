@@ -23,18 +23,15 @@
 // A binning overflow (hs_counters.overflow != 0) is seen ON THE DEVICE: the fold then writes nothing.
 //
 // This unit is compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS), so that the threshold tests below
-// see the bits the forward's saw; the expressions are the forward's and the backward's, operand for operand.  The helpers
-// marked "as render.hip" are restated here because that unit keeps them in its anonymous namespace and must not change.  Of
-// hs_cloud.h only the host-side argument checks are used.
-#include "hs_cloud.h"
+// see the bits the forward's saw; the expressions are the forward's and the backward's, operand for operand.  The forward's
+// decisions a replay repeats (pixel mapping, XCD strip map, staged conic, thresholds, pair_act bits, walk bound, pair slots),
+// the tile context, the segmented sum and the workspace layout are hs_replay.h's, shared with contrib.hip.
+#include "hs_replay.h"
 
 namespace hs {
 namespace {
 
-constexpr float kAlphaMin = 1.0f / 255.0f;
-constexpr float kAlphaMax = 0.99f;
 constexpr float kLogEps = 1e-8f;
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int kAThreads = 128;       // threads per workgroup: two waves, one per half tile
 // staged entries per batch (a multiple of 64, at most the threads).  Measured, whole call, two runs each: 128 entries 0.482 /
 // 0.481 ms at 1 M Gaussians / 1080p and 0.157 / 0.159 ms at 100 k / 800 x 800; 64 entries (half the LDS) 0.469 / 0.471 and
@@ -43,41 +40,6 @@ constexpr int kABatch = 128;
 
 static_assert(kABatch % 64 == 0 && kABatch <= kAThreads, "the lists are built from whole ballots, one entry is staged per thread");
 
-typedef float f2 __attribute__((ext_vector_type(2)));
-
-// ---- as render.hip ----
-__device__ __forceinline__ void scale_entry(float4& a, float4& b) {
-    a.z *= -0.5f * kLog2e; a.w *= -kLog2e; b.x *= -0.5f * kLog2e;
-}
-__device__ __forceinline__ void lane_pixels(int lane, int sx, int sy, int& px, int& py0) {
-    px = sx + 8 * (lane >> 5) + (lane & 7);
-    py0 = sy + 2 * ((lane >> 3) & 3);
-}
-__device__ __forceinline__ int xcd_strip_tile(int b, int nb, int gx) {
-    constexpr int kXcd = 8, kRows = 2;
-    const int x = b % kXcd, k = b / kXcd;
-    const int per = nb / kXcd, rem = nb % kXcd;
-    int p = x * per + min(x, rem) + k;
-    const int rows = nb / gx;
-    const int nstrips = (rows + kRows - 1) / kRows;
-    const int strip_tiles = kRows * gx;
-    const int last_short = nstrips * strip_tiles - nb;
-    int c = 0;
-    for (; c < kXcd - 1; ++c) {
-        const int ns = (nstrips - c + kXcd - 1) / kXcd;
-        const int nt = ns * strip_tiles - (((nstrips - 1) % kXcd) == c ? last_short : 0);
-        if (p < nt) break;
-        p -= nt;
-    }
-    const int s_local = p / strip_tiles, r = p - s_local * strip_tiles;
-    return (c + kXcd * s_local) * strip_tiles + r;
-}
-__device__ __forceinline__ float hs_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d));
-    return v;
-}
 __device__ __forceinline__ f2 splat(float v) { f2 r = {v, v}; return r; }
 // number of set bits of a wave-uniform 64-bit mask below this lane
 __device__ __forceinline__ int mask_prefix(uint64_t m) {
@@ -111,34 +73,29 @@ __device__ __forceinline__ float crf_grad_H(const Crf& c, int ch, float Hv, floa
     return g * (t[i + 1] - t[i]) * scale / xv * c.dt;
 }
 
-// ---- sum over the 32 lanes of a lane group (rows 2g, 2g + 1 of the wave): a fixed DPP tree -- the four in-row steps leave
-// every lane of a row with the row's total, row_bcast:15 then brings the first row's into the second.  Valid in lanes
-// 16..31 (group 0) and 48..63 (group 1); the other rows hold scratch.  Needs a full exec mask.  (As contrib.hip.)
-__device__ __forceinline__ float group_sum(float v) {
-    v += dpp_f32<0xB1>(v);        // quad_perm [1,0,3,2]
-    v += dpp_f32<0x4E>(v);        // quad_perm [2,3,0,1]
-    v += dpp_f32<0x141>(v);       // row_half_mirror
-    v += dpp_f32<0x140>(v);       // row_mirror
-    v += dpp_f32<0x142, 0xA>(v);  // row_bcast:15 -> rows 1,3
-    return v;
-}
-
-struct Replay {
-    int W, H, gx, gy, ntiles, N, F, flags;   // N: poses per FRAME, F: frames (the launch covers F x N poses)
-    int64_t capacity, I;                     // pair slots; instances (poses x Gaussians)
-    const hs_counters* counters;
-    const uint2* ranges; const uint32_t* point_list; const float4* rec; const float* bg;
-    const float* final_T; const uint32_t* n_contrib; const float* pose_hdr;
+struct Replay : ReplayFrame {
+    const float* bg; const float* final_T; const float* pose_hdr;
     const float* dL_dcolor; const float* dL_dhdr; const float* dL_dalpha; const float* dL_dinvdepth;
-    const uint8_t* pair_act;
     Crf crf;
+    // (here, beside the words the prologue loads anyway: as the first word behind the frame part it was fetched by a late
+    // scalar load of its own in front of the pixel loads, 0.5 % of the call at both measured sizes)
+    int flags;
     const float* exposure;
     float2* pair_rec;                        // out: one record per pair slot
 };
 
-// the record of a pair (the row of an instance) no pixel composited: sums of magnitudes are never negative
+// The sums of a set of |t_x|, |t_y| terms, and their 8-byte record.  The record of a pair (the row of an instance) no pixel
+// composited is {-1, -1}: sums of magnitudes are never negative.
 __device__ __forceinline__ float2 empty_record() { return make_float2(-1.f, -1.f); }
 __device__ __forceinline__ bool has_term(float2 v) { return !(v.x < 0.f); }
+struct AbsAcc {
+    typedef float2 Rec;
+    float sx = 0.f, sy = 0.f;
+    int any = 0;
+    __device__ __forceinline__ void take(const float2 v) { if (has_term(v)) { sx += v.x; sy += v.y; any = 1; } }
+    __device__ __forceinline__ void meet(int d) { sx += __shfl_xor(sx, d); sy += __shfl_xor(sy, d); any |= __shfl_xor(any, d); }
+    __device__ __forceinline__ float2 row() const { return any ? make_float2(sx, sy) : empty_record(); }
+};
 
 // Upstream gradient w.r.t. this pose's radiance H_ch at one pixel (as render.hip's pixel_grad).
 __device__ __forceinline__ float pixel_grad(const Replay& p, const Crf& c, int pose, int frame, int ch, int64_t pix, int64_t HW) {
@@ -182,15 +139,6 @@ __device__ __forceinline__ void load_pixel_bwd(const Replay& p, PixB& s, bool in
     s.dLd = (p.dL_dinvdepth && inside) ? p.dL_dinvdepth[pix] / (float)p.N : 0.f;
 }
 
-// slot of the (tile, instance) pair in duplicateWithKeys order: the arithmetic of render_bwd_kernel's write-out (integer
-// adds and float divides by a power of two: contraction cannot change it)
-__device__ __forceinline__ int64_t pair_slot(const Replay& p, float x, float y, int rad, uint32_t off, int tx, int ty) {
-    const int rminx = min(p.gx, max(0, (int)((x - (float)rad) / (float)kTile)));
-    const int rminy = min(p.gy, max(0, (int)((y - (float)rad) / (float)kTile)));
-    const int rmaxx = min(p.gx, max(0, (int)((x + (float)rad + (float)(kTile - 1)) / (float)kTile)));
-    return (int64_t)off + (int64_t)(ty - rminy) * (rmaxx - rminx) + (tx - rminx);
-}
-
 template <bool DEPTH>
 __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
     constexpr int KB = kABatch;
@@ -204,45 +152,25 @@ __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
     __shared__ uint16_t s_list[2][2][kListLen];   // [wave][lane group]: the group's takers among the staged entries, back to front
     __shared__ uint32_t s_max[2];
 
-    // an overflowed frame was rendered empty (its ranges are cleared) and adds nothing: the later kernels read no record
-    if (p.counters->overflow) return;
-    const int vt = xcd_strip_tile(blockIdx.x, gridDim.x, p.gx);  // virtual tile = pose * ntiles + tile
-    const int pose = vt / p.ntiles;
-    const int tile = vt - pose * p.ntiles;
-    const int tx = tile % p.gx, ty = tile / p.gx;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 5;
-    const int sx = tx * kTile, sy = ty * kTile + wave * 8;
-    int px, py0;
-    lane_pixels(lane, sx, sy, px, py0);
-    const int py1 = py0 + 1;
-    const bool in0 = px < p.W && py0 < p.H, in1 = px < p.W && py1 < p.H;
-    const float pxf = (float)px;
-    const f2 pyf = {(float)py0, (float)py1};
+    if (p.counters->overflow) return;     // (ReplayFrame: the frame adds nothing)
+    const TileCtx tc = tile_context(p);
+    const int wave = tc.wave, lane = tc.lane, plane = act_plane(tc.grp, tc.wave);
 
-    const uint2 range = p.ranges[vt];
-    // (a list lies inside the sorted pairs; anything else is not a state hs_forward left, and is walked as empty)
-    const int n = (range.y >= range.x && (int64_t)range.y <= p.capacity) ? (int)(range.y - range.x) : 0;
-
-    const int frame = p.F > 1 ? pose / p.N : 0;
     PixB s0, s1;
-    load_pixel_bwd(p, s0, in0, pose, frame, px, py0);
-    load_pixel_bwd(p, s1, in1, pose, frame, px, py1);
+    load_pixel_bwd(p, s0, tc.in0, tc.pose, tc.frame, tc.px, tc.py0);
+    load_pixel_bwd(p, s1, tc.in1, tc.pose, tc.frame, tc.px, tc.py1);
     f2 T = {s0.T, s1.T}, q = {s0.q, s1.q};
     const f2 dL0 = {s0.dL0, s1.dL0}, dL1 = {s0.dL1, s1.dL1}, dL2 = {s0.dL2, s1.dL2}, dLd = {s0.dLd, s1.dLd};
     const uint32_t last0 = s0.last, last1 = s1.last;
 
-    // the walk's bound: the tile's deepest contributor (pair_act is written for the entries the forward staged, and it
-    // staged at least these); never more than the list holds
-    const uint32_t wave_max = wave_max_u32(max(last0, last1));
-    if (lane == 0) s_max[wave] = wave_max;
+    post_wave_depth(s_max, tc, last0, last1);
     if (threadIdx.x == 0) {
         s_a[KB] = make_float4(0.f, 0.f, 0.f, 0.f); s_b[KB] = make_float4(0.f, 0.f, 0.f, 0.f); s_c[KB] = make_float4(0.f, 1.f, 0.f, 0.f);
     }
     __syncthreads();
-    const int n_proc = min(n, (int)max(s_max[0], s_max[1]));
+    const int n_proc = walk_bound(s_max, tc);
 
-    const uint16_t* const my_list = s_list[wave][grp];
+    const uint16_t* const my_list = s_list[wave][tc.grp];
     // |t_x| = |A dx + B dy| |w| W / 2 with A = -2 A2 / log2(e), B = -B2 / log2(e): the sums are kept in the staged (scaled)
     // conic's units, the positive factor is applied once per pair at write-out
     const float kx = 0.5f * (float)p.W / kLog2e, ky = 0.5f * (float)p.H / kLog2e;
@@ -254,8 +182,8 @@ __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
         __syncthreads();   // the previous batch's write-out has read its records
         uint32_t act = 0;
         if ((int)threadIdx.x < cnt) {
-            const uint32_t id = min(p.point_list[range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
-            act = p.pair_act[(int64_t)range.x + base + threadIdx.x];
+            const uint32_t id = min(p.point_list[tc.range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
+            act = p.pair_act[(int64_t)tc.range.x + base + threadIdx.x];
             const float4* r = p.rec + kRecF4 * (int64_t)id;
             float4 ra = r[0], rb = r[1];
             float4 rc = r[2];
@@ -275,7 +203,7 @@ __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
         int maxn = 0;
 #pragma unroll
         for (int g = 0; g < 2; ++g) {
-            const uint32_t gbit = 1u << (2 * g + wave);
+            const uint32_t gbit = 1u << act_plane(g, wave);
             uint16_t* lst = s_list[wave][g];
             int n_g = 0;
 #pragma unroll
@@ -299,8 +227,8 @@ __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
             const float4 b = s_b[j];
             const float4 c = s_c[j];
             // ---- the forward's alpha: same expressions, same operand order ----
-            const float dx = a.x - pxf;
-            const f2 dy = a.y - pyf;
+            const float dx = a.x - tc.pxf;
+            const f2 dy = a.y - tc.pyf;
             const float t = a.z * dx * dx, u = a.w * dx;
             const f2 pw = dy * (b.x * dy + u) + t;
             const f2 G = {hs_exp2(pw.x), hs_exp2(pw.y)};
@@ -332,71 +260,27 @@ __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
             // did a pixel of this lane group composite the entry?  (the forward's activity bit also covers the entry that
             // terminated a pixel, which is not composited)
             const uint64_t anym = __ballot(act0 || act1);
-            const bool any = (uint32_t)(anym >> (32 * grp)) != 0u;
+            const bool any = (uint32_t)(anym >> (32 * tc.grp)) != 0u;
             // one lane per group, a plain LDS store into the group's own plane of its own entry (the sentinel's is scratch)
-            if ((lane & 31) == 31) s_part[j][2 * grp + wave] = any ? make_float2(ax, ay) : empty_record();
+            if ((lane & 31) == 31) s_part[j][plane] = any ? make_float2(ax, ay) : empty_record();
         }
         __syncthreads();
         if ((int)threadIdx.x < cnt) {
             // the planes the entry's takers wrote (its activity bits), added in plane order
-            float2 o = make_float2(0.f, 0.f);
-            bool any = false;
+            AbsAcc o;
 #pragma unroll
-            for (int pl = 0; pl < 4; ++pl) {
-                if ((act >> pl) & 1u) {
-                    const float2 v = s_part[threadIdx.x][pl];
-                    if (has_term(v)) { o.x += v.x; o.y += v.y; any = true; }
-                }
-            }
-            o.x *= kx; o.y *= ky;
-            if (!any) o = empty_record();
+            for (int pl = 0; pl < 4; ++pl)
+                if ((act >> pl) & 1u) o.take(s_part[threadIdx.x][pl]);
+            o.sx *= kx; o.sy *= ky;
             const float4 a = s_a[threadIdx.x], c = s_c[threadIdx.x];
-            const int64_t slot = pair_slot(p, a.x, a.y, __float_as_int(c.z), __float_as_uint(c.w), tx, ty);
-            if (slot >= 0 && slot < p.capacity) p.pair_rec[slot] = o;
+            const int64_t slot = pair_slot(p, a.x, a.y, __float_as_int(c.z), __float_as_uint(c.w), tc.tx, tc.ty);
+            if (slot >= 0 && slot < p.capacity) p.pair_rec[slot] = o.row();
         }
     }
-    // the entries behind the tile's deepest contributor: nobody took them
-    for (int i = n_proc + (int)threadIdx.x; i < n; i += kAThreads) {
-        const uint32_t id = min(p.point_list[range.x + i], (uint32_t)(p.I - 1));
-        const float4* r = p.rec + kRecF4 * (int64_t)id;
-        const float4 ra = r[0], rc = r[2];
-        const int64_t slot = pair_slot(p, ra.x, ra.y, __float_as_int(rc.z), __float_as_uint(rc.w), tx, ty);
-        if (slot >= 0 && slot < p.capacity) p.pair_rec[slot] = empty_record();
-    }
+    write_untaken(p, tc, n_proc, kAThreads, p.pair_rec, empty_record());
 }
 
-struct Segsum {
-    int64_t I, capacity;
-    const uint32_t* inst_sorted; const uint32_t* offs_sorted; const hs_counters* counters;
-    const float2* pair_rec; float2* inst_rows;
-};
-
-// Thread t: instance t >> 2 (in depth order), quad lane t & 3 -- lane q combines records beg + q, beg + q + 4, ... in slot
-// order, the four partial results meet in a fixed butterfly (as contrib_segsum_kernel).
-__global__ void __launch_bounds__(256) absgrad_segsum_kernel(Segsum a) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t i = t >> 2;
-    const int q = (int)(t & 3);
-    // binning overflow: nothing was emitted or rendered, and slots past the capacity do not exist
-    const bool valid = i < a.I && !a.counters->overflow;
-    const uint32_t beg = valid ? (i == 0 ? 0u : a.offs_sorted[i - 1]) : 0u;
-    uint32_t end = valid ? a.offs_sorted[i] : 0u;
-    if ((int64_t)end > a.capacity) end = (uint32_t)a.capacity;
-    float sx = 0.f, sy = 0.f;
-    int any = 0;
-    for (uint32_t s = beg + q; s < end; s += 4) {
-        const float2 v = a.pair_rec[(int64_t)s];
-        if (has_term(v)) { sx += v.x; sy += v.y; any = 1; }
-    }
-    sx += __shfl_xor(sx, 1); sx += __shfl_xor(sx, 2);
-    sy += __shfl_xor(sy, 1); sy += __shfl_xor(sy, 2);
-    any |= __shfl_xor(any, 1); any |= __shfl_xor(any, 2);
-    if (i < a.I && q == 0) {
-        // (a depth sort that gave up -- overflow = 2 -- left no instance list: the empty row goes to row i)
-        const int64_t inst = a.counters->overflow ? i : (int64_t)a.inst_sorted[i];
-        if (inst < a.I) a.inst_rows[inst] = any ? make_float2(sx, sy) : empty_record();
-    }
-}
+__global__ void __launch_bounds__(256) absgrad_segsum_kernel(Segsum<float2> a) { segsum_rows<AbsAcc>(a); }
 
 // One thread per Gaussian, frames in ascending order: the rows of the frame's poses added in ascending pose order, then
 // abs_grad_accum += sqrt(a_x^2 + a_y^2) -- a call over F frames leaves what F single-frame calls leave.  A frame in which no
@@ -419,10 +303,6 @@ __global__ void __launch_bounds__(256) absgrad_fold_kernel(int P, int N, int F, 
     if (wrote) abs_grad_accum[g] = acc;
 }
 
-// workspace: pair records [capacity] | instance rows [P * n_poses], 8 bytes each, both 256-byte aligned
-int64_t pair_rec_bytes(const hs_dims& d) { return align_up(d.capacity * 8, 256); }
-int64_t inst_row_bytes(const hs_dims& d) { return align_up((int64_t)d.P * d.n_poses * 8, 256); }
-
 }  // namespace
 }  // namespace hs
 
@@ -434,8 +314,7 @@ HS_API int64_t hs_abs_gradient_workspace_bytes(const hs_dims* dims) {
     const char* fn = "hs_abs_gradient_workspace_bytes";
     hs_sizes sz;
     if (check_args(fn, dims) || hs_plan(dims, &sz, nullptr) != HS_OK) return HS_EINVAL;
-    const int64_t bytes = pair_rec_bytes(*dims) + inst_row_bytes(*dims);
-    return bytes > 0 ? bytes : 256;
+    return replay_workspace_bytes(*dims, sizeof(AbsAcc::Rec));
 }
 
 HS_API int hs_abs_gradient(const hs_abs_gradient_args* a, void* hip_stream) {
@@ -464,38 +343,25 @@ HS_API int hs_abs_gradient(const hs_abs_gradient_args* a, void* hip_stream) {
     if ((rc = check_aligned(fn, a->exposure, "exposure", 4)) != HS_OK) return rc;
     if ((rc = check_aligned(fn, a->crf_table, "crf_table", 4)) != HS_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    const char* geom = (const char*)a->geom; const char* bin = (const char*)a->binning; const char* img = (const char*)a->image;
-    const hs_counters* counters = (const hs_counters*)(geom + L.counters);
-    float2* pair_rec = (float2*)a->ws;
-    float2* inst_rows = (float2*)((char*)a->ws + pair_rec_bytes(d));
-    const int64_t I = (int64_t)d.P * d.n_poses;
 
     Replay p;
-    p.W = d.W; p.H = d.H; p.gx = (d.W + kTile - 1) / kTile; p.gy = (d.H + kTile - 1) / kTile;
-    p.ntiles = p.gx * p.gy; p.F = frames_of(d); p.N = d.n_poses / p.F; p.flags = a->flags;
-    p.capacity = d.capacity; p.I = I; p.counters = counters;
-    p.ranges = (const uint2*)(bin + L.ranges); p.point_list = (const uint32_t*)(bin + L.point_list);
-    p.rec = (const float4*)(geom + L.rec); p.bg = a->bg;
-    p.final_T = (const float*)(img + L.final_T); p.n_contrib = (const uint32_t*)(img + L.n_contrib);
-    p.pose_hdr = (const float*)(img + L.pose_hdr);
+    static_cast<ReplayFrame&>(p) = replay_frame(d, L, a->geom, a->binning, a->image);
+    const Segsum<float2> sg = replay_segsum<float2>(p, d, L, a->binning, a->ws);
+    p.flags = a->flags; p.bg = a->bg;
+    p.final_T = (const float*)((const char*)a->image + L.final_T); p.pose_hdr = (const float*)((const char*)a->image + L.pose_hdr);
     p.dL_dcolor = a->dL_dout_color; p.dL_dhdr = a->dL_dout_hdr; p.dL_dalpha = a->dL_dout_alpha;
     p.dL_dinvdepth = a->dL_dout_invdepth;
-    p.pair_act = (const uint8_t*)bin + L.pair_act;
     p.crf.table = a->crf_table; p.crf.K = a->crf_K; p.crf.umin = a->crf_umin; p.crf.umax = a->crf_umax; p.crf.dt = 1.f;
     p.exposure = a->exposure;
-    p.pair_rec = pair_rec;
+    p.pair_rec = sg.pair_rec;
     if (a->dL_dout_invdepth) absgrad_replay_kernel<true><<<p.ntiles * d.n_poses, kAThreads, 0, s>>>(p);
     else absgrad_replay_kernel<false><<<p.ntiles * d.n_poses, kAThreads, 0, s>>>(p);
     HS_LAUNCH_CHECK();
 
-    Segsum sg;
-    sg.I = I; sg.capacity = d.capacity;
-    sg.inst_sorted = (const uint32_t*)(bin + L.inst_sorted); sg.offs_sorted = (const uint32_t*)(bin + L.offs_sorted);
-    sg.counters = counters; sg.pair_rec = pair_rec; sg.inst_rows = inst_rows;
-    absgrad_segsum_kernel<<<ceil_div(4 * I, 256), 256, 0, s>>>(sg);
+    absgrad_segsum_kernel<<<ceil_div(4 * p.I, 256), 256, 0, s>>>(sg);
     HS_LAUNCH_CHECK();
 
-    absgrad_fold_kernel<<<ceil_div(d.P, 256), 256, 0, s>>>(d.P, p.N, p.F, counters, inst_rows, a->abs_grad_accum);
+    absgrad_fold_kernel<<<ceil_div(d.P, 256), 256, 0, s>>>(d.P, p.N, p.F, p.counters, sg.inst_rows, a->abs_grad_accum);
     HS_LAUNCH_CHECK();
     return HS_OK;
 }

@@ -1,6 +1,6 @@
 // Shared by the translation units that work on the cloud rather than on a frame: adam, densify, activate, knn, mcmc, mcmc_reg,
-// smoothing, and api (which checks the arguments of hs_activate).  The rasterizer's units do not include it; contrib.hip takes
-// the host-side argument checks only.
+// smoothing, and api (which checks the arguments of hs_activate).  The rasterizer's units do not include it; the replay units
+// (hs_replay.h: contrib, absgrad) take the host-side argument checks only.
 //
 // Every unit that uses the float helpers below is compiled with -ffp-contract=off (Makefile, FAST_TUS), and they
 // STATE an order of operations: each line is a sequence of correctly rounded IEEE operations around the library expf / sqrtf,
