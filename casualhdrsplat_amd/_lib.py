@@ -200,6 +200,16 @@ class hs_abs_gradient_args(C.Structure):
                 ("abs_grad_accum", _fp)]
 
 
+class hs_composite_features_args(C.Structure):
+    _fields_ = [("dims", hs_dims), ("geom", _fp), ("binning", _fp), ("image", _fp), ("n_channels", C.c_int32),
+                ("reserved", C.c_int32), ("features", _fp), ("out", _fp)]
+
+
+class hs_composite_features_bwd_args(C.Structure):
+    _fields_ = [("dims", hs_dims), ("geom", _fp), ("binning", _fp), ("image", _fp), ("ws", _fp), ("n_channels", C.c_int32),
+                ("reserved", C.c_int32), ("dL_dout", _fp), ("dL_dfeatures", _fp)]
+
+
 class hs_bilagrid_args(C.Structure):
     _fields_ = [("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("G", C.c_int32), ("L", C.c_int32), ("Y", C.c_int32),
                 ("X", C.c_int32), ("reserved", C.c_int32),
@@ -292,6 +302,9 @@ SIGNATURES = {
     "hs_vq_update": _call(hs_vq_args),
     "hs_undistort_map": _call(hs_undistort_args),
     "hs_undistort_remap": _call(hs_undistort_args),
+    "hs_composite_features_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
+    "hs_composite_features": _call(hs_composite_features_args),
+    "hs_composite_features_backward": _call(hs_composite_features_bwd_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

@@ -129,19 +129,12 @@ __global__ void __launch_bounds__(kCBatch) contrib_replay_kernel(Replay p) {
                 const float4 a = s_a[j];
                 const float4 b = s_b[j];
                 const bool on = (s_actb[j] & gbit) != 0;   // this lane's block took the entry (the forward evaluated it there)
-                // ---- the forward's alpha: same expressions, same operand order ----
-                const float dx = a.x - tc.pxf;
-                const f2 dy = a.y - tc.pyf;
-                const float t = a.z * dx * dx, u = a.w * dx;
-                const f2 pw = dy * (b.x * dy + u) + t;
-                const float al0 = fminf(kAlphaMax, b.y * hs_exp2(pw.x));
-                const float al1 = fminf(kAlphaMax, b.y * hs_exp2(pw.y));
-                // ---- the three tests of blend_fwd_pair: power <= 0, alpha >= 1/255, and "before the entry at which
-                // T (1 - alpha) < 1e-4 ends the pixel" -- the forward's own answer to the third is n_contrib
+                // ---- the forward's alpha and the three tests of blend_fwd_pair (hs_replay.h) ----
+                const PairAlpha al = pair_alpha(tc, a, b);
                 const uint32_t idx = (uint32_t)(base + j);
-                const bool act0 = on && idx < last0 && pw.x <= 0.f && al0 >= kAlphaMin;
-                const bool act1 = on && idx < last1 && pw.y <= 0.f && al1 >= kAlphaMin;
-                const f2 alpha = {al0, al1};
+                const bool act0 = composited(on, idx, last0, al.pw.x, al.al0);
+                const bool act1 = composited(on, idx, last1, al.pw.y, al.al1);
+                const f2 alpha = {al.al0, al.al1};
                 const f2 one = {1.f, 1.f};
                 const f2 test_T = T * (one - alpha);
                 const f2 aT = alpha * T;

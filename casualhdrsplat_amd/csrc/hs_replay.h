@@ -1,7 +1,8 @@
 // Shared by the units that REPLAY a finished render to keep a per-Gaussian statistic that exists only inside the compositing
-// loop: contrib.hip (blending weights, front to back) and absgrad.hip (AbsGS, back to front).  A replay has to reproduce the
+// loop: contrib.hip (blending weights, front to back) and absgrad.hip (AbsGS, back to front) -- and by features.hip, which
+// composites further per-Gaussian channels with those weights.  A replay has to reproduce the
 // forward's decisions bit for bit, and this header is the ONE restatement of them outside render.hip: the pixel mapping, the
-// XCD strip map, the staged conic, the alpha thresholds, the pair_act bits, the walk bound, the pair slots, and around them
+// XCD strip map, the staged conic, the alpha expressions and thresholds, the pair_act bits, the walk bound, the pair slots, and around them
 // what every replay is built from -- the frame part of the kernel argument, the per-workgroup tile context, the records
 // behind the deepest contributor, the per-instance segmented sum and the workspace layout.
 //
@@ -128,6 +129,27 @@ __device__ __forceinline__ TileCtx tile_context(const ReplayFrame& p) {
     c.n = (c.range.y >= c.range.x && (int64_t)c.range.y <= p.capacity) ? (int)(c.range.y - c.range.x) : 0;
     c.frame = p.F > 1 ? c.pose / p.N : 0;
     return c;
+}
+
+// ---- the forward's alpha of a staged entry (a = {x, y, A2, B2}, b.x = C2, b.y = opacity, after scale_entry) at the lane's
+// pixel pair: the forward's expressions in the forward's operand order (as render.hip's blend_fwd_pair) ----
+struct PairAlpha { f2 pw; float al0, al1; };
+
+__device__ __forceinline__ PairAlpha pair_alpha(const TileCtx& c, const float4 a, const float4 b) {
+    PairAlpha r;
+    const float dx = a.x - c.pxf;
+    const f2 dy = a.y - c.pyf;
+    const float t = a.z * dx * dx, u = a.w * dx;
+    r.pw = dy * (b.x * dy + u) + t;
+    r.al0 = fminf(kAlphaMax, b.y * hs_exp2(r.pw.x));
+    r.al1 = fminf(kAlphaMax, b.y * hs_exp2(r.pw.y));
+    return r;
+}
+// The three tests of blend_fwd_pair at one pixel: power <= 0, alpha >= 1/255, and "before the entry at which
+// T (1 - alpha) < 1e-4 ends the pixel" -- the forward's own answer to the third is n_contrib (`last`); `on`: the lane's
+// block took the entry (pair_act: the forward evaluated it there)
+__device__ __forceinline__ bool composited(bool on, uint32_t idx, uint32_t last, float pw, float al) {
+    return on && idx < last && pw <= 0.f && al >= kAlphaMin;
 }
 
 // ---- the walk's bound: the tile's deepest contributor (n_contrib of its pixels: pair_act is written for the entries the

@@ -1031,6 +1031,69 @@ typedef struct hs_abs_gradient_args {
 HS_API int64_t hs_abs_gradient_workspace_bytes(const hs_dims* dims);
 HS_API int hs_abs_gradient(const hs_abs_gradient_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Per-Gaussian feature compositing (features.hip): C extra channels stored per
+ * Gaussian -- a semantic or language feature field, a depth or a normal, a per-Gaussian statistic to look at -- composited
+ * per pixel with the blending weights of a finished hs_forward call.  The forward composites three channels (the SH
+ * radiance) plus accumulated opacity and inverse depth; this is a front-to-back replay of it from the state it left in the
+ * three workspaces (rec, point_list, ranges, n_contrib, pair_act), for any number of further channels, without another
+ * preprocess, binning, sort or render pass.  WHAT the features hold stays with the trainer.
+ *
+ * Definition.  For one finished hs_forward call with n_poses poses and a feature matrix features[P, C] (fp32, row-major,
+ * 1 <= C <= 512): take every pose k, every pixel p and every entry g that the published rule composites at (k, p) -- the
+ * decisions of hs_contribution's definition above; the forward's own answer to them is pair_act and n_contrib -- with
+ * w = alpha * T_before.
+ *   Forward.   out[k, c, p] = sum of w * features[g, c] over those entries in list order (front to back), accumulated by
+ *     fp32 fma.  Layout [n_poses, C, H, W]; pose k of frame f is index f * N + k.  No background term, no 1 / N, no pose
+ *     average (the blur average of a frame is the mean over its N images, taken by the caller).  A pixel nothing reaches is
+ *     +0.  EVERY element of out is written, also in tiles with an empty list and for a call whose binning overflowed
+ *     (hs_counters.overflow != 0: all zeros, decided on the device).  An entry that is not composited at a pixel adds nothing
+ *     there -- it is selected out, not multiplied by zero: a non-finite feature of a Gaussian reaches only the pixels the
+ *     Gaussian is composited on.
+ *   Backward.  dL_dfeatures[g, c] = sum over k, p of w * dL_dout[k, c, p].  WRITTEN, not accumulated, every element; a
+ *     Gaussian nothing reached gets +0, an overflowed frame gives all zeros.  Per instance the (tile, instance) pair records
+ *     are summed in slot order; per Gaussian the sum starts at +0 and adds the poses' rows in ascending pose order.  No
+ *     atomics: the same inputs give the same bits.  A non-finite dL_dout at a pixel reaches only the Gaussians composited
+ *     there.
+ * The outputs carry NO gradient to the geometry (means, covariances, opacities): that would be a C-channel generalisation
+ * of the render backward and is out of scope -- w is a constant of both calls.
+ *
+ * The forward is one kernel and needs no workspace.  The backward runs passes of three kernels (the replay: one record of
+ * the pass's channel sums per (tile, instance) pair at the pair's duplicateWithKeys slot; a fixed-order sum of every
+ * instance's contiguous slots; the fold over the poses) -- eight channels per pass (32-byte records) while more than four
+ * are left, then four (16-byte records) -- over one workspace of its own, whose size does not depend on C:
+ * hs_composite_features_workspace_bytes(dims) = align256(32 * capacity) + align256(32 * P * n_poses) (256 when that is 0),
+ * 256-byte aligned; every word is written before it is read.  The three state workspaces are only read.
+ * HS_EINVAL (reported before any HIP call): null args; dims that hs_plan refuses; n_channels outside [1, 512]; a null out
+ * (forward); with P > 0 a null geom, binning, image, features (forward) or ws, dL_dout, dL_dfeatures (backward) (workspaces
+ * 256-byte, arrays 4-byte aligned).  P == 0: the forward writes out (zeros), the backward is a successful no-op. */
+typedef struct hs_composite_features_args {
+    hs_dims dims;                 /* the dims of the hs_forward call */
+    const void* geom;             /* state produced by hs_forward (same buffers), read only */
+    const void* binning;
+    const void* image;
+    int32_t n_channels;           /* C */
+    int32_t reserved;
+    const float* features;        /* [P,C]; rows are read 16 bytes at a time when C % 4 == 0 and this is 16-byte aligned */
+    float* out;                   /* [n_poses,C,H,W] */
+} hs_composite_features_args;
+
+typedef struct hs_composite_features_bwd_args {
+    hs_dims dims;                 /* the dims of the hs_forward call */
+    const void* geom;             /* state produced by hs_forward (same buffers), read only */
+    const void* binning;
+    const void* image;
+    void* ws;                     /* hs_composite_features_workspace_bytes(&dims) bytes, 256-byte aligned */
+    int32_t n_channels;           /* C */
+    int32_t reserved;
+    const float* dL_dout;         /* [n_poses,C,H,W] */
+    float* dL_dfeatures;          /* [P,C] */
+} hs_composite_features_bwd_args;
+
+/* (backward only) a positive multiple of 256, non-decreasing in capacity; -1 (HS_EINVAL) for dims that hs_plan refuses */
+HS_API int64_t hs_composite_features_workspace_bytes(const hs_dims* dims);
+HS_API int hs_composite_features(const hs_composite_features_args* args, void* hip_stream);
+HS_API int hs_composite_features_backward(const hs_composite_features_bwd_args* args, void* hip_stream);
+
 /* (detected by name; HS_VERSION unchanged) Bilateral-grid image correction ("Bilateral Guided Radiance Field Processing",
  * SIGGRAPH 2024), fused (bilagrid.hip): every frame owns a small 3-D lattice of 3 x 4 affine colour matrices addressed by pixel
  * position and luma; the rendered image is sliced through it between the rasterizer and the loss, and a total-variation term
