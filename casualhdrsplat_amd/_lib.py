@@ -210,6 +210,14 @@ class hs_composite_features_bwd_args(C.Structure):
                 ("reserved", C.c_int32), ("dL_dout", _fp), ("dL_dfeatures", _fp)]
 
 
+class hs_composite_features_geometry_args(C.Structure):
+    _fields_ = [("dims", hs_dims), ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("scale_modifier", C.c_float),
+                ("flags", C.c_int32), ("viewmatrices", _fp), ("projmatrices", _fp), ("camposes", _fp), ("means3D", _fp),
+                ("opacities", _fp), ("scales", _fp), ("rotations", _fp), ("geom", _fp), ("binning", _fp), ("image", _fp),
+                ("ws", _fp), ("n_channels", C.c_int32), ("reserved", C.c_int32), ("features", _fp), ("dL_dout", _fp),
+                ("dL_dmeans3D", _fp), ("dL_dopacities", _fp), ("dL_dscales", _fp), ("dL_drotations", _fp)]
+
+
 class hs_bilagrid_args(C.Structure):
     _fields_ = [("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("G", C.c_int32), ("L", C.c_int32), ("Y", C.c_int32),
                 ("X", C.c_int32), ("reserved", C.c_int32),
@@ -305,6 +313,8 @@ SIGNATURES = {
     "hs_composite_features_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
     "hs_composite_features": _call(hs_composite_features_args),
     "hs_composite_features_backward": _call(hs_composite_features_bwd_args),
+    "hs_composite_features_geometry_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
+    "hs_composite_features_geometry_backward": _call(hs_composite_features_geometry_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

@@ -20,8 +20,8 @@
 // The backward runs its passes (eight channels while more than four are left, then four) over one workspace sized for the
 // 32-byte records of an eight-channel pass: twice hs_contribution's, whatever C is.
 //
-// No gradient reaches the geometry (means, covariances, opacities) through these outputs: that is a C-channel generalisation
-// of render_bwd_kernel and out of scope.
+// The gradient these kernels deliver reaches the features; the gradient to the geometry (means, covariances, opacities)
+// through the channels -- a C-channel generalisation of render_bwd_kernel -- is featgeo.hip's.
 //
 // Compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS); the forward's decisions are hs_replay.h's.
 #include "hs_replay.h"

@@ -1054,8 +1054,9 @@ HS_API int hs_abs_gradient(const hs_abs_gradient_args* args, void* hip_stream);
  *     are summed in slot order; per Gaussian the sum starts at +0 and adds the poses' rows in ascending pose order.  No
  *     atomics: the same inputs give the same bits.  A non-finite dL_dout at a pixel reaches only the Gaussians composited
  *     there.
- * The outputs carry NO gradient to the geometry (means, covariances, opacities): that would be a C-channel generalisation
- * of the render backward and is out of scope -- w is a constant of both calls.
+ * w is a constant of both calls: the gradient these two deliver reaches the features.  The gradient of the same loss with
+ * respect to the GEOMETRY (means, covariances, opacities) through the channels is a call of its own,
+ * hs_composite_features_geometry_backward below.
  *
  * The forward is one kernel and needs no workspace.  The backward runs passes of three kernels (the replay: one record of
  * the pass's channel sums per (tile, instance) pair at the pair's duplicateWithKeys slot; a fixed-order sum of every
@@ -1093,6 +1094,70 @@ typedef struct hs_composite_features_bwd_args {
 HS_API int64_t hs_composite_features_workspace_bytes(const hs_dims* dims);
 HS_API int hs_composite_features(const hs_composite_features_args* args, void* hip_stream);
 HS_API int hs_composite_features_backward(const hs_composite_features_bwd_args* args, void* hip_stream);
+
+/* (detected by name; HS_VERSION unchanged) Gradients to the GEOMETRY through the composited channels (featgeo.hip): what a
+ * loss on the output of hs_composite_features asks of the means, scales, rotations and opacities of the forward behind it --
+ * the render backward for C channels instead of three.
+ *
+ * Definition.  Input: a finished hs_forward, features[P, C] and dL_dout[n_poses, C, H, W] (the gradient with respect to the
+ * output of hs_composite_features).  At pose k, pixel p and entry i composited there -- the decisions hs_composite_features
+ * uses -- let d_i = sum over c of features[g_i, c] * dL_dout[k, c, p].  No background term, no 1 / N and no CRF: the output of
+ * hs_composite_features has none.  Back to front, with q = 0 behind the deepest contributor and T from the forward's final
+ * transmittance (T_i = T_{i+1} / (1 - alpha_i)):
+ *     dL/dalpha_i = T_i (d_i - q_i),    q_{i-1} = q_i + alpha_i (d_i - q_i)
+ * -- the render backward's recurrence with c_i . dL replaced by d_i and the background, accumulated-opacity and
+ * inverse-depth terms absent.  From dL/dalpha on everything is the render backward's: the terms of the 2-D mean, the conic and
+ * the opacity, operand for operand, and the projection of hs_backward (HS_BWD_PROJECT) from there to the 3-D mean, the
+ * scales, the rotations and the opacities (HS_FLAG_ANTIALIAS as in the forward).  The 0.99 cap on alpha behaves as in
+ * hs_backward: the gradient passes through it.
+ * Outputs.  dL_dmeans3D [P,3], dL_dopacities [P], dL_dscales [P,3], dL_drotations [P,4]: WRITTEN, not accumulated, every
+ * element, summed over all poses of the call (every frame's).  They are the gradients with respect to the arrays the forward
+ * took (the activated ones); a caller that also ran hs_backward adds the two.  An overflowed frame
+ * (hs_counters.overflow != 0) gives all zeros, decided on the device.
+ * Order.  Channels go in passes of sixteen (the last pass: the narrowest of 4, 8, 16 that holds the rest); d is linear in the
+ * channels, so the passes' pair records add, in ascending pass order, each by the one thread that owns the record; per
+ * instance the records are summed in slot order (as hs_backward's), per Gaussian the poses in ascending order.  No atomics:
+ * the same inputs give the same bits.
+ * State.  The three workspaces of the forward are only READ -- in particular the pair flags hs_backward keeps in the
+ * binning workspace are not written: hs_backward may run before or after this call on the same state.  The records
+ * (hs_backward's 64-byte pair records, colour and inverse-depth slots zero), their flags and the per-instance rows live in
+ * a workspace of the call's own: hs_composite_features_geometry_workspace_bytes(dims) = align256(64 * capacity) +
+ * align256(64 * P * n_poses) + align256(capacity) (256 when that is 0), 256-byte aligned, its size independent of C; every
+ * word the call reads from it is one the call wrote.
+ * HS_EINVAL (reported before any HIP call): null args; dims that hs_plan refuses; n_channels outside [1, 512]; with P > 0 a
+ * null scales / rotations (a forward with cov3D_precomp is NOT supported) or any other null pointer; a misaligned one
+ * (workspaces 256-byte, rotations and dL_drotations 16-byte, the other arrays 4-byte).  P == 0: a successful no-op.
+ * Out of scope, each a later change: camera-pose gradients through the channels (the projection could deliver them);
+ * dL_dmeans2D and the densification statistics through the channels; cov3D_precomp; normalisation of the channels by the
+ * accumulated opacity; the wiring into a captured step (graphs.GraphedStep). */
+typedef struct hs_composite_features_geometry_args {
+    hs_dims dims;                 /* the dims of the hs_forward call */
+    float tanfovx, tanfovy, scale_modifier;   /* as in the forward */
+    int32_t flags;                /* the forward's HS_FLAG_* (HS_FLAG_ANTIALIAS is the one that is read) */
+    const float* viewmatrices;    /* [n_poses,16], as in the forward */
+    const float* projmatrices;    /* [n_poses,16] */
+    const float* camposes;        /* [n_poses,3] */
+    const float* means3D;         /* [P,3], as the forward took them */
+    const float* opacities;       /* [P] */
+    const float* scales;          /* [P,3] */
+    const float* rotations;       /* [P,4], 16-byte aligned */
+    const void* geom;             /* state produced by hs_forward (same buffers), read only */
+    const void* binning;
+    const void* image;
+    void* ws;                     /* hs_composite_features_geometry_workspace_bytes(&dims) bytes, 256-byte aligned */
+    int32_t n_channels;           /* C */
+    int32_t reserved;
+    const float* features;        /* [P,C]; rows are read 16 bytes at a time when C % 4 == 0 and this is 16-byte aligned */
+    const float* dL_dout;         /* [n_poses,C,H,W] */
+    float* dL_dmeans3D;           /* [P,3] */
+    float* dL_dopacities;         /* [P] */
+    float* dL_dscales;            /* [P,3] */
+    float* dL_drotations;         /* [P,4], 16-byte aligned */
+} hs_composite_features_geometry_args;
+
+/* a positive multiple of 256, non-decreasing in capacity and in P * n_poses; -1 (HS_EINVAL) for dims that hs_plan refuses */
+HS_API int64_t hs_composite_features_geometry_workspace_bytes(const hs_dims* dims);
+HS_API int hs_composite_features_geometry_backward(const hs_composite_features_geometry_args* args, void* hip_stream);
 
 /* (detected by name; HS_VERSION unchanged) Bilateral-grid image correction ("Bilateral Guided Radiance Field Processing",
  * SIGGRAPH 2024), fused (bilagrid.hip): every frame owns a small 3-D lattice of 3 x 4 affine colour matrices addressed by pixel
