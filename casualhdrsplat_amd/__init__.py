@@ -15,13 +15,15 @@ bilateral-grid colour correction between the rasterizer's image and the loss (bi
 bilagrid.tv_loss), and the k-means codebook compression of a finished cloud's view-dependent SH coefficients (vq.quantize_sh,
 vq.kmeans, scene_io.save_vq), and the lens undistortion of captured frames, fused with the downscale to the training resolution
 (undistort.undistort_map, undistort.undistort_frames, undistort.undistorted_camera), and the compositing of any number of
-per-Gaussian feature channels with a finished forward's blending weights (features.composite_features).  Compute lives in
+per-Gaussian feature channels with a finished forward's blending weights (features.composite_features), and the depth-distortion
+regulariser on the blending weights of a ray (distortion.distortion_loss).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
 """
 from .bilagrid import BilateralGrid, slice_image, tv_loss
 from .densify import DensifyResult, densify_and_prune
+from .distortion import distortion_loss
 from .features import composite_features
 from .importance import ContributionStats, accumulate_abs_gradients, accumulate_contributions
 from .knn import knn_mean_dist2
@@ -43,5 +45,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats"
            "prune_rows", "keep_top_k", "densify_top_k", "RowsResult", "BilateralGrid", "slice_image", "tv_loss",
            "kmeans", "kmeans_assign", "kmeans_update", "quantize_sh", "dequantize_sh", "VQResult",
            "undistorted_camera", "undistort_map", "undistort_frames", "UndistortMap",
-           "composite_features"]
+           "composite_features", "distortion_loss"]
 __version__ = "0.1.0"

@@ -218,6 +218,18 @@ class hs_composite_features_geometry_args(C.Structure):
                 ("dL_dmeans3D", _fp), ("dL_dopacities", _fp), ("dL_dscales", _fp), ("dL_drotations", _fp)]
 
 
+class hs_distortion_args(C.Structure):
+    _fields_ = [("dims", hs_dims), ("geom", _fp), ("binning", _fp), ("image", _fp), ("out_distortion", _fp), ("out_moment", _fp)]
+
+
+class hs_distortion_bwd_args(C.Structure):
+    _fields_ = [("dims", hs_dims), ("tanfovx", C.c_float), ("tanfovy", C.c_float), ("scale_modifier", C.c_float),
+                ("flags", C.c_int32), ("viewmatrices", _fp), ("projmatrices", _fp), ("camposes", _fp), ("means3D", _fp),
+                ("opacities", _fp), ("scales", _fp), ("rotations", _fp), ("geom", _fp), ("binning", _fp), ("image", _fp),
+                ("ws", _fp), ("moment", _fp), ("dL_ddistortion", _fp),
+                ("dL_dmeans3D", _fp), ("dL_dopacities", _fp), ("dL_dscales", _fp), ("dL_drotations", _fp)]
+
+
 class hs_bilagrid_args(C.Structure):
     _fields_ = [("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("G", C.c_int32), ("L", C.c_int32), ("Y", C.c_int32),
                 ("X", C.c_int32), ("reserved", C.c_int32),
@@ -315,6 +327,9 @@ SIGNATURES = {
     "hs_composite_features_backward": _call(hs_composite_features_bwd_args),
     "hs_composite_features_geometry_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
     "hs_composite_features_geometry_backward": _call(hs_composite_features_geometry_args),
+    "hs_distortion_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
+    "hs_distortion": _call(hs_distortion_args),
+    "hs_distortion_backward": _call(hs_distortion_bwd_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

@@ -1,7 +1,7 @@
 // Shared by the units that REPLAY a finished render to keep a per-Gaussian statistic that exists only inside the compositing
 // loop: contrib.hip (blending weights, front to back) and absgrad.hip (AbsGS, back to front) -- and by features.hip, which
 // composites further per-Gaussian channels with those weights, and featgeo.hip, the backward of that compositing to the
-// geometry (back to front).  A replay has to reproduce the
+// geometry (back to front), and distort.hip, the depth-distortion loss of the blending weights (both directions).  A replay has to reproduce the
 // forward's decisions bit for bit, and this header is the ONE restatement of them outside render.hip: the pixel mapping, the
 // XCD strip map, the staged conic, the alpha expressions and thresholds, the pair_act bits, the walk bound, the pair slots, and around them
 // what every replay is built from -- the frame part of the kernel argument, the per-workgroup tile context, the records

@@ -15,6 +15,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --batch-frames         # all frames of a step in ONE rasterizer call
     python examples/train_synthetic.py --steps 300 --mcmc                 # learn the WHOLE cloud from a quarter of the points: MCMC policy
     python examples/train_synthetic.py --steps 300 --mcmc --filter-3d     # ... with the 3D smoothing filter of Mip-Splatting
+    python examples/train_synthetic.py --steps 300 --mcmc --distortion 1  # ... with the depth-distortion regulariser on the blending weights
     python examples/train_synthetic.py --steps 300 --topk                 # ... grown by score to a budget, pruned by contribution
     python examples/train_synthetic.py --steps 200 --absgrad              # ... the published densify / prune on the AbsGS statistic
     python examples/train_synthetic.py --steps 300 --topk --absgrad       # ... the budgeted policy, scored by the AbsGS statistic
@@ -44,6 +45,7 @@ from casualhdrsplat_amd.importance import ContributionStats, accumulate_contribu
 from casualhdrsplat_amd.mcmc import grow, inject_noise, regularize, relocate
 from casualhdrsplat_amd.rows import densify_top_k, keep_top_k
 from casualhdrsplat_amd.densify import densify_and_prune
+from casualhdrsplat_amd.distortion import distortion_loss
 from casualhdrsplat_amd.optim import cloud_param_groups
 from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.optim import GaussianAdam
@@ -76,7 +78,7 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
         mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False, absgrad=False,
-        bilagrid=False, distort=None, vq=0):
+        bilagrid=False, distort=None, vq=0, distortion=None):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -125,7 +127,17 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     (vq.quantize_sh, 10 iterations) -- weighted by the blending-weight sums of a pass over all frames
     (ContributionStats.weight_sum) where the learner's rasterizers keep the state that pass needs (topk, absgrad), unweighted
     otherwise --, every frame is rendered again from the dequantised cloud, and the result gains `vq`: the PSNR between the
-    two renders and the sizes of the cloud as scene_io.save_ply and as scene_io.save_vq write it."""
+    two renders and the sizes of the cloud as scene_io.save_ply and as scene_io.save_vq write it.
+    distortion = LAMBDA >= 0: the depth-distortion regulariser of Mip-NeRF 360 on every frame's blending weights
+    (distortion.distortion_loss on the rasterizer's output, with the tensors the forward was given): LAMBDA times the mean of
+    the [virtual, H, W] map is added to each frame's loss, and the history gains `distortion`, that mean averaged over the
+    frames.  LAMBDA = 0 adds nothing and computes the map without a gradient: the run to compare with.  Works with every
+    eager mode, with and without batch_frames; not with graph=True."""
+    if distortion is not None and graph:
+        raise ValueError("distortion=LAMBDA (--distortion) is not supported together with graph=True (--graph): the term is "
+                         "not wired into the captured step")
+    if distortion is not None and distortion < 0:
+        raise ValueError("distortion=LAMBDA (--distortion) must be >= 0")
     if vq and deg < 1:
         raise ValueError("vq=K (--vq K) needs deg >= 1 (--deg): a degree-0 cloud has no view-dependent coefficients to quantise")
     if bilagrid and graph:
@@ -262,6 +274,18 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         grid_ids = torch.arange(frames, dtype=torch.int32, device=dev)
         learn.append(grids.grids)
 
+    dist_mean = {"value": None}            # --distortion: the mean of the step's distortion maps (a device scalar)
+
+    def distortion_term(ldr, opac):
+        """LAMBDA * mean(map) of the forward behind `ldr` (None for LAMBDA = 0); the mean goes to dist_mean"""
+        if distortion > 0:
+            geo = dict(means3D=cur["means3D"], opacities=opac, scales=cur["scales"], rotations=cur["rotations"])
+            m = distortion_loss(ldr, geo).mean()
+        else:
+            m = distortion_loss(ldr).mean()
+        dist_mean["value"] = m.detach() if dist_mean["value"] is None else dist_mean["value"] + m.detach()
+        return distortion * m if distortion > 0 else None
+
     def backward_of(step_loss):
         """backward of the step's loss, with gsplat's 10 tv(grids) added under --bilagrid"""
         if bilagrid:
@@ -279,8 +303,10 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         cams = model.cameras_all()
         opac = cur["opacities"] if raw else torch.sigmoid(raw_opac)
         losses, mses = [], []
+        dist_mean["value"] = None
         for i in range(frames):
             ldr, _, radii, _ = model(i, cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"], cameras=cams)
+            reg = distortion_term(ldr, opac) if distortion is not None else None
             if bilagrid:
                 ldr = grids(ldr, i)
             if fused_adam and not whole:   # (kernels only, written in place: the captured step leaves no copy node behind)
@@ -292,6 +318,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                 losses.append(photometric_loss(ldr, targets[i], lambda_dssim))
             else:
                 losses.append(mean_by_rows((ldr - targets[i]).abs()))
+            if reg is not None:
+                losses[-1] = losses[-1] + reg
             mses.append(mean_by_rows((ldr.detach() - targets[i]) ** 2))
         backward_of(torch.stack(losses).sum())
         return torch.stack([l_.detach() for l_ in losses]), torch.stack(mses)
@@ -306,6 +334,11 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             p_.grad = None
         opac = cur["opacities"] if raw else torch.sigmoid(raw_opac)
         ldr, _, radii, _ = model.forward_frames(range(frames), cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"])
+        dist_mean["value"] = None
+        # (one map over every pose of every frame: its mean is the mean of the per-frame means; the step's loss is their sum)
+        reg = distortion_term(ldr, opac) if distortion is not None else None
+        if dist_mean["value"] is not None:
+            dist_mean["value"] = dist_mean["value"] * frames
         if bilagrid:
             ldr = grids(ldr, grid_ids)
         if fused_adam and not whole:
@@ -317,6 +350,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         else:
             losses = torch.stack([mean_by_rows((ldr[i] - targets[i]).abs()) for i in range(frames)])
         mses = torch.stack([mean_by_rows((ldr[i].detach() - targets[i]) ** 2) for i in range(frames)])
+        if reg is not None:
+            losses = torch.cat([losses, (reg * frames).reshape(1)])
         backward_of(losses.sum())
         return losses.detach(), mses
 
@@ -364,6 +399,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         if bilagrid:
             extra["tv"] = float(grid_tv["value"])
             total += frames * 10.0 * extra["tv"]
+        if distortion is not None:
+            extra["distortion"] = float(dist_mean["value"]) / frames
         if it < steps:
             if bilagrid:
                 grid_opt.step()
@@ -493,6 +530,9 @@ def main(argv=None):
                     help="after training, quantise the view-dependent SH coefficients to K centroids (needs --deg >= 1; weighted by "
                          "the blending-weight sums under --topk / --absgrad), render every frame again from the dequantised cloud and "
                          "print the PSNR between the two renders and both file sizes")
+    ap.add_argument("--distortion", type=float, default=None, metavar="LAMBDA",
+                    help="add LAMBDA times the mean depth-distortion map of every frame (distortion.distortion_loss) to its loss and "
+                         "print that mean; 0 prints it without adding the term; eager only (not with --graph)")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
@@ -501,10 +541,12 @@ def main(argv=None):
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
             refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk,
-            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq)
+            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq, distortion=a.distortion)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")
+    if a.distortion is not None:
+        print(f"mean distortion map {f['distortion']:.6f} -> {l['distortion']:.6f} (lambda {a.distortion:g})")
     if a.vq:
         v = r["vq"]
         print(f"vq K {v['K']} ({'weighted by contribution' if v['weighted'] else 'unweighted'}), P {v['P']}: PSNR full vs quantised "

@@ -1159,6 +1159,87 @@ typedef struct hs_composite_features_geometry_args {
 HS_API int64_t hs_composite_features_geometry_workspace_bytes(const hs_dims* dims);
 HS_API int hs_composite_features_geometry_backward(const hs_composite_features_geometry_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Depth-distortion loss (distort.hip): the regulariser of Mip-NeRF 360 on the
+ * blending weights of a ray (2DGS uses it, gsplat ships it as distloss), per pixel of a finished hs_forward call.  It pulls
+ * the weights of a ray together and starves floaters and semi-transparent haze.  Quadratic in the weights and built from
+ * prefix sums along the ray, it exists only inside the compositing loop: a front-to-back replay of the forward's state for the
+ * map, a back-to-front replay for its gradient to the geometry.
+ *
+ * Definition.  At pose k and pixel p take the entries i = 1..n the forward composited there -- the decisions
+ * hs_composite_features uses (pair_act, n_contrib) -- front to back, with w_i = alpha_i * T_i, s_i = 1 / z_i (the instance's
+ * view-space depth as stored in the render record: the 1 / z that out_invdepth composites), A_i = sum over j <= i of w_j and
+ * D_i = sum over j <= i of w_j s_j:
+ *     distortion[k, p] = 2 * sum over i of w_i * (D_{i-1} - s_i * A_{i-1})
+ *     moment[k, p]     = D_n                   (sum w s: the expected inverse depth of that pose)
+ * A list is sorted by the fp32 bits of z and a correctly rounded reciprocal is monotone, so s is non-increasing along the
+ * list and the sum equals sum_i sum_j w_i w_j |s_i - s_j| >= 0.  No background term, no 1 / N, no pose average, no
+ * normalisation.  Layout [n_poses, H, W]; pose k of frame f is index f * N + k.  A pixel with fewer than two contributors
+ * gives exactly +0.  EVERY element of both outputs is written; a call whose binning overflowed (hs_counters.overflow != 0)
+ * gives all zeros, decided on the device.  s is the inverse depth, not z: it is bounded (z > 0.2 gives s < 5), it is what the
+ * library already composites, and its gradient path to the mean exists.  The loss is invariant under s -> s - s0, and the
+ * kernels carry their sums relative to a workgroup-uniform s0 (1 / z of the tile's first entry); moment is sum w s.
+ * Backward.  With gamma = dL/d distortion[k, p], back to front with A_n = 1 - final_T, D_n = moment, q = 0 behind the deepest
+ * contributor, T rebuilt from the forward's final transmittance (T_i = T_{i+1} / (1 - alpha_i)), A+_i and D+_i the sums over
+ * j > i:
+ *     v_i        = 2 * [ (D_{i-1} - s_i A_{i-1}) + (s_i A+_i - D+_i) ]      (= dL_p / dw_i)
+ *     dL/dalpha_i = gamma * T_i * (v_i - q_i),    q_{i-1} = q_i + alpha_i (v_i - q_i)
+ *     dL/ds_i   += gamma * 2 * w_i * (A+_i - A_{i-1})
+ * -- hs_composite_features_geometry_backward's recurrence with d_i = gamma v_i (L_p depends on alpha only through w).  From
+ * dL/dalpha on the terms of the 2-D mean, the conic and the opacity are the render backward's, operand for operand; the sum
+ * over the pixels of dL/ds_i goes into the inverse-depth slot of the pair record and reaches the 3-D mean through z in the
+ * projection of hs_backward (HS_BWD_PROJECT).  The 0.99 cap on alpha passes the gradient through.
+ * Outputs of the backward.  dL_dmeans3D [P,3], dL_dopacities [P], dL_dscales [P,3], dL_drotations [P,4]: WRITTEN, not
+ * accumulated, every element, summed over all poses of the call, with respect to the arrays the forward took (the activated
+ * ones).  An overflowed frame gives all zeros.  Per instance the pair records are summed in slot order, per Gaussian the
+ * poses in ascending order.  No atomics: the same inputs give the same bits.
+ * State.  The three workspaces of the forward are only READ: hs_backward may run before or after on the same state.  The
+ * backward's records, flags and rows live in a workspace of the call's own: hs_distortion_workspace_bytes(dims) =
+ * align256(64 * capacity) + align256(64 * P * n_poses) + align256(capacity) (256 when that is 0), 256-byte aligned; every
+ * word the call reads from it is one the call wrote.  The forward needs no workspace.
+ * HS_EINVAL (reported before any HIP call): null args; dims that hs_plan refuses; a null or misaligned out_distortion /
+ * out_moment (forward); with P > 0 a null scales / rotations (a forward with cov3D_precomp is NOT supported) or any other
+ * null pointer; a misaligned one (workspaces 256-byte, rotations and dL_drotations 16-byte, the other arrays 4-byte).
+ * P == 0: the forward writes zeros, the backward is a successful no-op that looks at no pointer.
+ * Out of scope, each a later change: distortion in linear z or a near / far normalisation; the per-frame pose average;
+ * camera-pose gradients, dL_dmeans2D and the densification statistics through the term; the wiring into a captured step. */
+typedef struct hs_distortion_args {
+    hs_dims dims;                 /* the dims of the hs_forward call */
+    const void* geom;             /* state produced by hs_forward (same buffers), read only */
+    const void* binning;
+    const void* image;
+    float* out_distortion;        /* [n_poses,H,W] */
+    float* out_moment;            /* [n_poses,H,W] */
+} hs_distortion_args;
+
+typedef struct hs_distortion_bwd_args {
+    hs_dims dims;                 /* the dims of the hs_forward call */
+    float tanfovx, tanfovy, scale_modifier;   /* as in the forward */
+    int32_t flags;                /* the forward's HS_FLAG_* (HS_FLAG_ANTIALIAS is the one that is read) */
+    const float* viewmatrices;    /* [n_poses,16], as in the forward */
+    const float* projmatrices;    /* [n_poses,16] */
+    const float* camposes;        /* [n_poses,3] */
+    const float* means3D;         /* [P,3], as the forward took them */
+    const float* opacities;       /* [P] */
+    const float* scales;          /* [P,3] */
+    const float* rotations;       /* [P,4], 16-byte aligned */
+    const void* geom;             /* state produced by hs_forward (same buffers), read only */
+    const void* binning;
+    const void* image;
+    void* ws;                     /* hs_distortion_workspace_bytes(&dims) bytes, 256-byte aligned */
+    const float* moment;          /* [n_poses,H,W], what hs_distortion wrote into out_moment */
+    const float* dL_ddistortion;  /* [n_poses,H,W] */
+    float* dL_dmeans3D;           /* [P,3] */
+    float* dL_dopacities;         /* [P] */
+    float* dL_dscales;            /* [P,3] */
+    float* dL_drotations;         /* [P,4], 16-byte aligned */
+} hs_distortion_bwd_args;
+
+/* (backward only) a positive multiple of 256, non-decreasing in capacity and in P * n_poses; -1 (HS_EINVAL) for dims that
+ * hs_plan refuses */
+HS_API int64_t hs_distortion_workspace_bytes(const hs_dims* dims);
+HS_API int hs_distortion(const hs_distortion_args* args, void* hip_stream);
+HS_API int hs_distortion_backward(const hs_distortion_bwd_args* args, void* hip_stream);
+
 /* (detected by name; HS_VERSION unchanged) Bilateral-grid image correction ("Bilateral Guided Radiance Field Processing",
  * SIGGRAPH 2024), fused (bilagrid.hip): every frame owns a small 3-D lattice of 3 x 4 affine colour matrices addressed by pixel
  * position and luma; the rendered image is sliced through it between the rasterizer and the loss, and a total-variation term
