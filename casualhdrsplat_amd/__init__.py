@@ -16,7 +16,8 @@ bilagrid.tv_loss), and the k-means codebook compression of a finished cloud's vi
 vq.kmeans, scene_io.save_vq), and the lens undistortion of captured frames, fused with the downscale to the training resolution
 (undistort.undistort_map, undistort.undistort_frames, undistort.undistorted_camera), and the compositing of any number of
 per-Gaussian feature channels with a finished forward's blending weights (features.composite_features), and the depth-distortion
-regulariser on the blending weights of a ray (distortion.distortion_loss).  Compute lives in
+regulariser on the blending weights of a ray (distortion.distortion_loss), and the depth-normal consistency term with the
+per-Gaussian normals it composites (normals.normal_consistency_loss, normals.gaussian_normals).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
@@ -29,6 +30,7 @@ from .importance import ContributionStats, accumulate_abs_gradients, accumulate_
 from .knn import knn_mean_dist2
 from .losses import photometric_loss, ssim
 from .mcmc import GrowResult, RelocateResult, grow, inject_noise, regularize, relocate
+from .normals import gaussian_normals, normal_consistency_loss
 from .optim import GaussianAdam, cloud_param_groups
 from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSettings, GaussianRasterizer,
                          SortChainStalled, inspect_state, rasterize_gaussians)
@@ -45,5 +47,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats"
            "prune_rows", "keep_top_k", "densify_top_k", "RowsResult", "BilateralGrid", "slice_image", "tv_loss",
            "kmeans", "kmeans_assign", "kmeans_update", "quantize_sh", "dequantize_sh", "VQResult",
            "undistorted_camera", "undistort_map", "undistort_frames", "UndistortMap",
-           "composite_features", "distortion_loss"]
+           "composite_features", "distortion_loss", "normal_consistency_loss", "gaussian_normals"]
 __version__ = "0.1.0"

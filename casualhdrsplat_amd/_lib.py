@@ -261,6 +261,18 @@ class hs_undistort_args(C.Structure):
                 ("map", _fp), ("valid", _fp), ("frames", _fp), ("out", _fp)]
 
 
+class hs_normal_consistency_args(C.Structure):
+    _fields_ = [("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
+                ("invdepth", _fp), ("alpha", _fp), ("normals", _fp), ("weight", _fp), ("cam_to_world", _fp),
+                ("out", _fp), ("depth_normals", _fp), ("dL_dout", _fp), ("dL_dnormals", _fp), ("dL_dinvdepth", _fp),
+                ("dL_dalpha", _fp), ("workspace", _fp)]
+
+
+class hs_gaussian_normals_args(C.Structure):
+    _fields_ = [("P", C.c_int64), ("rotations", _fp), ("scales", _fp), ("means3D", _fp), ("campos", _fp), ("normals", _fp),
+                ("dL_dnormals", _fp), ("dL_drotations", _fp)]
+
+
 def _call(args):
     """int f(const args*, void* hip_stream): the shape of most entry points"""
     return C.c_int, [C.POINTER(args), C.c_void_p]
@@ -330,6 +342,11 @@ SIGNATURES = {
     "hs_distortion_workspace_bytes": (_i64, [C.POINTER(hs_dims)]),
     "hs_distortion": _call(hs_distortion_args),
     "hs_distortion_backward": _call(hs_distortion_bwd_args),
+    "hs_normal_consistency_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "hs_normal_consistency": _call(hs_normal_consistency_args),
+    "hs_normal_consistency_backward": _call(hs_normal_consistency_args),
+    "hs_gaussian_normals": _call(hs_gaussian_normals_args),
+    "hs_gaussian_normals_backward": _call(hs_gaussian_normals_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

@@ -16,6 +16,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --mcmc                 # learn the WHOLE cloud from a quarter of the points: MCMC policy
     python examples/train_synthetic.py --steps 300 --mcmc --filter-3d     # ... with the 3D smoothing filter of Mip-Splatting
     python examples/train_synthetic.py --steps 300 --mcmc --distortion 1  # ... with the depth-distortion regulariser on the blending weights
+    python examples/train_synthetic.py --steps 300 --mcmc --normal 0.05   # ... with the depth-normal consistency term on the composited normals
     python examples/train_synthetic.py --steps 300 --topk                 # ... grown by score to a budget, pruned by contribution
     python examples/train_synthetic.py --steps 200 --absgrad              # ... the published densify / prune on the AbsGS statistic
     python examples/train_synthetic.py --steps 300 --topk --absgrad       # ... the budgeted policy, scored by the AbsGS statistic
@@ -46,6 +47,8 @@ from casualhdrsplat_amd.mcmc import grow, inject_noise, regularize, relocate
 from casualhdrsplat_amd.rows import densify_top_k, keep_top_k
 from casualhdrsplat_amd.densify import densify_and_prune
 from casualhdrsplat_amd.distortion import distortion_loss
+from casualhdrsplat_amd.features import composite_features
+from casualhdrsplat_amd.normals import gaussian_normals, normal_consistency_loss
 from casualhdrsplat_amd.optim import cloud_param_groups
 from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.optim import GaussianAdam
@@ -78,7 +81,7 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
         mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False, absgrad=False,
-        bilagrid=False, distort=None, vq=0, distortion=None):
+        bilagrid=False, distort=None, vq=0, distortion=None, normal=None):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -132,7 +135,21 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     (distortion.distortion_loss on the rasterizer's output, with the tensors the forward was given): LAMBDA times the mean of
     the [virtual, H, W] map is added to each frame's loss, and the history gains `distortion`, that mean averaged over the
     frames.  LAMBDA = 0 adds nothing and computes the map without a gradient: the run to compare with.  Works with every
-    eager mode, with and without batch_frames; not with graph=True."""
+    eager mode, with and without batch_frames; not with graph=True.
+    normal = LAMBDA >= 0: the depth-normal consistency term (normals.normal_consistency_loss) on every frame.  The learner's
+    rasterizers also return the accumulated opacity and the expected inverse depth; the per-Gaussian normals
+    (normals.gaussian_normals, turned to the frame's mid pose) are composited with the frame's blending weights
+    (features.composite_features with the geometry) and LAMBDA times the mean of the map, weighted by the detached alpha, is
+    added to the frame's loss.  With more than one virtual pose per frame this is an APPROXIMATION: the term sees the pose
+    average of the composited normals, of the alpha and of the inverse depth, with the mid pose's rotation -- not a term per
+    pose.  The history gains `normal`, the mean of the map averaged over the frames.  LAMBDA = 0 computes the map without a
+    gradient: the run to compare with.  Not with graph=True or batch_frames=True (neither delivers the optional outputs)."""
+    if normal is not None and (graph or batch_frames):
+        raise ValueError("normal=LAMBDA (--normal) is not supported together with graph=True (--graph) or batch_frames=True "
+                         "(--batch-frames): the term needs the rasterizer's return_alpha / return_invdepth outputs, which "
+                         "neither delivers")
+    if normal is not None and normal < 0:
+        raise ValueError("normal=LAMBDA (--normal) must be >= 0")
     if distortion is not None and graph:
         raise ValueError("distortion=LAMBDA (--distortion) is not supported together with graph=True (--graph): the term is "
                          "not wired into the captured step")
@@ -199,6 +216,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     # --graph: one persistent sync-free rasterizer per captured frame, so that the step's gradient computation can be
     # recorded once and replayed (graphs.GraphedStep): no host time for the few thousand tiny kernels of the pose arithmetic
     how = {"parameterization": "raw"} if raw else {}
+    if normal is not None:
+        how.update(return_alpha=True, return_invdepth=True)
     per_frame = FrameRasterizers(capacity=capacity or 40 * P * virtual, **how) if graph else None
     factory = per_frame if graph else (functools.partial(GaussianRasterizer, **how) if raw else None)
     filt = {"filter_3D": None}          # --filter-3d: the filter of the moment, handed to every rasterizer the learner makes
@@ -211,6 +230,18 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             score["last"] = GaussianRasterizer(settings, densify_stats=None if score["keep_state"] else score["stats"],
                                                keep_state=score["keep_state"], **how)
             return score["last"]
+    geom_out = {}                       # --normal: the accumulated opacity and inverse depth of the learner's last forward
+    if normal is not None:
+        make = factory if factory is not None else functools.partial(GaussianRasterizer, **how)
+
+        def factory(settings):
+            rast = make(settings)
+
+            def call(*args, **kw):          # (the formation unpacks colour, radii, hdr: the two extra images stay here)
+                out = rast(*args, **kw)
+                geom_out["alpha"], geom_out["invdepth"] = out[-2], out[-1]
+                return out[:-2]
+            return call
     model = formation(ImplicitCRF(K=128), **({"rasterizer_factory": factory} if factory is not None else {}))
     model.crf.load_state_dict(truth.crf.state_dict())
     for p_ in model.crf.parameters():
@@ -286,6 +317,22 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         dist_mean["value"] = m.detach() if dist_mean["value"] is None else dist_mean["value"] + m.detach()
         return distortion * m if distortion > 0 else None
 
+    normal_mean = {"value": None}          # --normal: the mean of the step's normal-consistency maps (a device scalar)
+    fx, fy = W / (2.0 * cam.tanfovx), H / (2.0 * cam.tanfovy)
+
+    def normal_term(ldr, opac, views, camposes):
+        """LAMBDA * mean(map) of the forward behind `ldr` (None for LAMBDA = 0); the mean goes to normal_mean"""
+        mid = views.shape[0] // 2
+        with torch.enable_grad() if normal > 0 else torch.no_grad():
+            n = gaussian_normals(cur["rotations"], cur["scales"], cur["means3D"], camposes[mid].detach().to(torch.float32))
+            geo = dict(means3D=cur["means3D"], opacities=opac, scales=cur["scales"], rotations=cur["rotations"])
+            N = composite_features(ldr, n, geometry=geo if normal > 0 else None).mean(dim=0)
+            alpha, invd = geom_out["alpha"], geom_out["invdepth"]
+            m = normal_consistency_loss(invd, N, fx, fy, alpha=alpha, weight=alpha.detach(),
+                                        cam_to_world=views[mid, :3, :3].detach().to(torch.float32)).mean()
+        normal_mean["value"] = m.detach() if normal_mean["value"] is None else normal_mean["value"] + m.detach()
+        return normal * m if normal > 0 else None
+
     def backward_of(step_loss):
         """backward of the step's loss, with gsplat's 10 tv(grids) added under --bilagrid"""
         if bilagrid:
@@ -304,9 +351,13 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
         opac = cur["opacities"] if raw else torch.sigmoid(raw_opac)
         losses, mses = [], []
         dist_mean["value"] = None
+        normal_mean["value"] = None
         for i in range(frames):
             ldr, _, radii, _ = model(i, cur["means3D"], opac, cur["shs"], cur["scales"], cur["rotations"], cameras=cams)
             reg = distortion_term(ldr, opac) if distortion is not None else None
+            if normal is not None:
+                reg_n = normal_term(ldr, opac, cams[0][i], cams[2][i])
+                reg = reg_n if reg is None else (reg if reg_n is None else reg + reg_n)
             if bilagrid:
                 ldr = grids(ldr, i)
             if fused_adam and not whole:   # (kernels only, written in place: the captured step leaves no copy node behind)
@@ -401,6 +452,8 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             total += frames * 10.0 * extra["tv"]
         if distortion is not None:
             extra["distortion"] = float(dist_mean["value"]) / frames
+        if normal is not None:
+            extra["normal"] = float(normal_mean["value"]) / frames
         if it < steps:
             if bilagrid:
                 grid_opt.step()
@@ -533,6 +586,12 @@ def main(argv=None):
     ap.add_argument("--distortion", type=float, default=None, metavar="LAMBDA",
                     help="add LAMBDA times the mean depth-distortion map of every frame (distortion.distortion_loss) to its loss and "
                          "print that mean; 0 prints it without adding the term; eager only (not with --graph)")
+    ap.add_argument("--normal", type=float, default=None, metavar="LAMBDA",
+                    help="add LAMBDA times the mean depth-normal consistency map of every frame (normals.normal_consistency_loss on "
+                         "the composited normals.gaussian_normals, weighted by the detached alpha) to its loss and print that mean; "
+                         "0 prints it without adding the term.  With more than one virtual pose per frame this is an approximation: "
+                         "the term is applied to the pose average of the composited normals, alpha and inverse depth, with the mid "
+                         "pose's rotation.  Eager only: not with --graph or --batch-frames")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
@@ -541,12 +600,14 @@ def main(argv=None):
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
             refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk,
-            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq, distortion=a.distortion)
+            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq, distortion=a.distortion, normal=a.normal)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")
     if a.distortion is not None:
         print(f"mean distortion map {f['distortion']:.6f} -> {l['distortion']:.6f} (lambda {a.distortion:g})")
+    if a.normal is not None:
+        print(f"mean normal-consistency map {f['normal']:.6f} -> {l['normal']:.6f} (lambda {a.normal:g})")
     if a.vq:
         v = r["vq"]
         print(f"vq K {v['K']} ({'weighted by contribution' if v['weighted'] else 'unweighted'}), P {v['P']}: PSNR full vs quantised "

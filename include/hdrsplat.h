@@ -1395,6 +1395,87 @@ HS_API int hs_undistort_map(const hs_undistort_args* args, void* hip_stream);
 /* reads map, frames; writes out */
 HS_API int hs_undistort_remap(const hs_undistort_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Depth-normal consistency (normals.hip): the regulariser 2DGS, GOF, RaDe-GS, PGSR
+ * and dn-splatter pair with the distortion term -- the composited per-Gaussian normals must agree with the normals of the
+ * surface the composited depth describes.
+ *
+ * Shapes.  invdepth, alpha, weight, out, dL_dout, dL_dinvdepth, dL_dalpha: [B, H, W] fp32; normals, depth_normals,
+ * dL_dnormals: [B, 3, H, W] fp32 planar; cam_to_world [B, 3, 3] fp32 row-major IN DEVICE MEMORY.  The principal point is the
+ * centre of the frame.
+ * Forward, per frame b and pixel (x, y).  d = invdepth (sum w / z, what out_invdepth holds), a = alpha (NULL: 1).  A sample is
+ * VALID when d and a are finite and > 0; its depth is z = a / d.  P(x, y) = z ((x + 0.5 - W / 2) / fx, (y + 0.5 - H / 2) / fy, 1).
+ * A pixel is INTERIOR when 1 <= x <= W - 2, 1 <= y <= H - 2 and it and its four axis neighbours are valid.  There
+ * c = (P(x, y+1) - P(x, y-1)) x (P(x+1, y) - P(x-1, y)), n_d = c / |c|, n = R_b n_d (cam_to_world NULL: n = n_d), and
+ * out[b, y, x] = w (1 - sum_k normals[b, k, y, x] n_k) with w = weight (NULL: 1); depth_normals[b, :, y, x] = n.  Elsewhere
+ * out and depth_normals are exactly 0; a frame with W < 3 or H < 3 is a valid call that gives zeros.  With positive depths
+ * c . P < 0: the normal faces the camera and |c| > 0.  The kernel evaluates fx fy c / (s_x s_y) (s = the sum of the two
+ * depths of an axis, a positive factor) from r = (difference) / (sum) per axis: (fx r_x, fy r_y, -(r_y yh + r_x xh + 1)) --
+ * the same direction without the cancellation in a difference of z u and without overflow; the fp32 operation order is
+ * stated at the top of normals.hip and restated, with a rounding bound per element, by tests/normals_reference.py.
+ * `normals` is used as given (no normalisation: sum w n of composite_features has length <= alpha).
+ * Range.  Validity is decided on d and a alone, as stated: a valid sample whose quotient a / d underflows to 0 or overflows to
+ * infinity in fp32 (a / d outside about [1e-38, 3e38]) stays valid, and NaN then reaches out and the gradients of the pixels
+ * whose stencil it sits in.  Depths a renderer produces are far inside; nothing clamps them here.
+ * Backward.  dL_dnormals_k = -dL_dout w n_k at interior pixels; dL_dinvdepth and dL_dalpha collect, per sample, the
+ * contributions of the four pixels whose stencil the sample sits in (through z = a / d: dz/dd = -z / d, dz/da = 1 / d) -- a
+ * gather in a fixed order, no atomics: the same inputs give the same bits.  Each of the three is written only when its
+ * pointer is given, and then EVERY element is written: exactly 0 at invalid samples and at samples (pixels) that feed no
+ * interior pixel.  weight, fx, fy and cam_to_world are constants.  All three NULL: a no-op.
+ * Limits (HS_EINVAL, reported before any HIP call): args non-null; B, H, W >= 1, 3 B H W < 2^31; fx, fy finite and > 0;
+ * invdepth non-null; forward: out or depth_normals given, normals non-null when out is; backward: normals and dL_dout
+ * non-null, dL_dalpha only with alpha; every pointer given 4-byte aligned.  The caller owns every byte, nothing is allocated,
+ * cleared or copied, the work is enqueued on the caller's stream and nothing synchronises: one launch each way. */
+typedef struct hs_normal_consistency_args {
+    int32_t B, H, W;
+    int32_t reserved;
+    float fx, fy;
+    const float* invdepth;        /* [B, H, W] */
+    const float* alpha;           /* [B, H, W], or NULL: 1 */
+    const float* normals;         /* [B, 3, H, W] */
+    const float* weight;          /* [B, H, W], or NULL: 1 */
+    const float* cam_to_world;    /* [B, 3, 3] row-major, device memory, or NULL: the identity */
+    float* out;                   /* [B, H, W] written by the forward, or NULL: skipped */
+    float* depth_normals;         /* [B, 3, H, W] written by the forward, or NULL: skipped */
+    const float* dL_dout;         /* [B, H, W] (backward) */
+    float* dL_dnormals;           /* [B, 3, H, W] written by the backward, or NULL: skipped */
+    float* dL_dinvdepth;          /* [B, H, W] written by the backward, or NULL: skipped */
+    float* dL_dalpha;             /* [B, H, W] written by the backward, or NULL: skipped (NULL when alpha is) */
+    void* workspace;              /* hs_normal_consistency_workspace_bytes(B, H, W) bytes: none today, may be NULL, never touched */
+} hs_normal_consistency_args;
+
+/* 0: the backward keeps the halo of its gather in LDS.  -1 (HS_EINVAL) outside the limits above.  No HIP call. */
+HS_API int64_t hs_normal_consistency_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* reads invdepth, alpha, normals, weight, cam_to_world; writes out, depth_normals */
+HS_API int hs_normal_consistency(const hs_normal_consistency_args* args, void* hip_stream);
+/* reads the same and dL_dout; writes dL_dnormals, dL_dinvdepth, dL_dalpha */
+HS_API int hs_normal_consistency_backward(const hs_normal_consistency_args* args, void* hip_stream);
+
+/* The per-Gaussian normal that is composited (normals.hip): the shortest axis of the ellipsoid, turned to the camera.
+ * q = rotations[i] = (w, x, y, z), qh = q / |q|, R(qh) the rotation the rasterizer builds; k = the index of the smallest of
+ * scales[i] (the lowest index on a tie; any monotone map of the scales gives the same k: stored log-scales may be passed);
+ * n0 = column k of R; normals[i] = n0 when n0 . (campos - means3D[i]) >= 0, else -n0.  |q| = 0: normals[i] = 0.
+ * |q| is sqrt of the fp32 sum of squares: a quaternion with a NaN or infinite component, or one whose sum of squares
+ * overflows (|q| above about 1e19) or underflows to 0 (|q| below about 1e-23), counts as |q| = 0: zeros both ways; between
+ * 1e-23 and 1e-19 the squares are subnormal and the normal loses precision.  Stored quaternions are of order 1.
+ * Backward: dL_drotations through R and the normalisation, k and the sign constants; |q| = 0: 0.  scales, means3D and
+ * campos receive nothing.  One thread per Gaussian, one launch each way.
+ * Limits (HS_EINVAL, before any HIP call): args non-null, 0 <= P < 2^30; P > 0: rotations and dL_drotations non-null and
+ * 16-byte aligned, scales, means3D, campos (3 floats IN DEVICE MEMORY), normals / dL_dnormals non-null and 4-byte aligned.
+ * P = 0 is a valid call that launches nothing and looks at no pointer. */
+typedef struct hs_gaussian_normals_args {
+    int64_t P;
+    const float* rotations;       /* [P, 4] */
+    const float* scales;          /* [P, 3] */
+    const float* means3D;         /* [P, 3] */
+    const float* campos;          /* [3], device memory */
+    float* normals;               /* [P, 3] written by the forward */
+    const float* dL_dnormals;     /* [P, 3] (backward) */
+    float* dL_drotations;         /* [P, 4] written by the backward */
+} hs_gaussian_normals_args;
+
+HS_API int hs_gaussian_normals(const hs_gaussian_normals_args* args, void* hip_stream);
+HS_API int hs_gaussian_normals_backward(const hs_gaussian_normals_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
