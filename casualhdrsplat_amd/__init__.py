@@ -17,7 +17,9 @@ vq.kmeans, scene_io.save_vq), and the lens undistortion of captured frames, fuse
 (undistort.undistort_map, undistort.undistort_frames, undistort.undistorted_camera), and the compositing of any number of
 per-Gaussian feature channels with a finished forward's blending weights (features.composite_features), and the depth-distortion
 regulariser on the blending weights of a ray (distortion.distortion_loss), and the depth-normal consistency term with the
-per-Gaussian normals it composites (normals.normal_consistency_loss, normals.gaussian_normals).  Compute lives in
+per-Gaussian normals it composites (normals.normal_consistency_loss, normals.gaussian_normals), and the fusion of rendered
+depth maps into a truncated signed distance volume with the triangle mesh extracted from it (tsdf.TSDFVolume,
+scene_io.save_mesh_ply).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
@@ -36,6 +38,7 @@ from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSet
                          SortChainStalled, inspect_state, rasterize_gaussians)
 from .rows import RowsResult, densify_top_k, keep_top_k, prune_rows
 from .smoothing import apply_filter_3D, compute_filter_3D
+from .tsdf import TSDFVolume
 from .undistort import UndistortMap, undistort_frames, undistort_map, undistorted_camera
 from .vq import VQResult, dequantize_sh, kmeans, kmeans_assign, kmeans_update, quantize_sh
 
@@ -47,5 +50,6 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats"
            "prune_rows", "keep_top_k", "densify_top_k", "RowsResult", "BilateralGrid", "slice_image", "tv_loss",
            "kmeans", "kmeans_assign", "kmeans_update", "quantize_sh", "dequantize_sh", "VQResult",
            "undistorted_camera", "undistort_map", "undistort_frames", "UndistortMap",
-           "composite_features", "distortion_loss", "normal_consistency_loss", "gaussian_normals"]
+           "composite_features", "distortion_loss", "normal_consistency_loss", "gaussian_normals",
+           "TSDFVolume"]
 __version__ = "0.1.0"

@@ -273,6 +273,15 @@ class hs_gaussian_normals_args(C.Structure):
                 ("dL_dnormals", _fp), ("dL_drotations", _fp)]
 
 
+class hs_tsdf_args(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("F", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("origin", C.c_float * 3), ("voxel_size", C.c_float), ("trunc", C.c_float), ("fx", C.c_float), ("fy", C.c_float),
+                ("min_alpha", C.c_float), ("max_depth", C.c_float), ("min_weight", C.c_float),
+                ("tsdf", _fp), ("weight", _fp), ("color", _fp), ("invdepth", _fp), ("alpha", _fp), ("frame_color", _fp),
+                ("viewmatrices", _fp), ("workspace", _fp), ("totals", _fp), ("n_vertices", C.c_int64), ("n_faces", C.c_int64),
+                ("vertices", _fp), ("faces", _fp), ("colors", _fp)]
+
+
 def _call(args):
     """int f(const args*, void* hip_stream): the shape of most entry points"""
     return C.c_int, [C.POINTER(args), C.c_void_p]
@@ -347,6 +356,10 @@ SIGNATURES = {
     "hs_normal_consistency_backward": _call(hs_normal_consistency_args),
     "hs_gaussian_normals": _call(hs_gaussian_normals_args),
     "hs_gaussian_normals_backward": _call(hs_gaussian_normals_args),
+    "hs_tsdf_integrate": _call(hs_tsdf_args),
+    "hs_tsdf_mesh_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "hs_tsdf_mesh_plan": _call(hs_tsdf_args),
+    "hs_tsdf_mesh_emit": _call(hs_tsdf_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

@@ -208,6 +208,80 @@ def load_vq(path: str) -> GaussianCloud:
         return GaussianCloud(t("means3D"), torch.from_numpy(shs), t("opacity_logit"), t("log_scales"), t("rotations"))
 
 
+# ------------------------------------------------------------------------------------------- triangle meshes
+def _host(x, dtype) -> np.ndarray:
+    return np.ascontiguousarray(x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x), dtype=dtype)
+
+
+def save_mesh_ply(path: str, vertices, faces, colors=None) -> None:
+    """A triangle mesh (tsdf.TSDFVolume.extract_mesh) as binary little-endian PLY, the layout mesh viewers read: element
+    vertex (float x y z[, uchar red green blue]) and element face (list uchar int vertex_indices).  vertices [V, 3] float,
+    faces [T, 3] integer, colors [V, 3] float or None: clamped to [0, 1] (a NaN: 0) and stored as round(255 c)."""
+    v, f = _host(vertices, "<f4"), _host(faces, "<i4")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"save_mesh_ply: vertices must be [V, 3] and faces [T, 3], got {v.shape} and {f.shape}")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError(f"save_mesh_ply: a face index outside the {v.shape[0]} vertices")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        c = _host(colors, np.float64)
+        if c.shape != v.shape:
+            raise ValueError(f"save_mesh_ply: colors must be {list(v.shape)}, got {c.shape}")
+        rgb = np.floor(np.clip(np.nan_to_num(c, nan=0.0), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vt = np.empty(v.shape[0], dtype=np.dtype(fields))
+    for i, n in enumerate("xyz"):
+        vt[n] = v[:, i]
+    if colors is not None:
+        for i, n in enumerate(("red", "green", "blue")):
+            vt[n] = rgb[:, i]
+    ft = np.empty(f.shape[0], dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    ft["n"] = 3
+    ft["i"] = f
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % v.shape[0]
+    header += "".join(f"property {'float' if t == '<f4' else 'uchar'} {n}\n" for n, t in fields)
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % f.shape[0]
+    with open(path, "wb") as out:
+        out.write(header.encode("ascii"))
+        out.write(vt.tobytes())
+        out.write(ft.tobytes())
+
+
+def load_mesh_ply(path: str):
+    """(vertices [V, 3] float32, faces [T, 3] int32, colors [V, 3] uint8 or None) of a file save_mesh_ply wrote."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        lines = []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: truncated PLY header")
+            lines.append(line.decode("ascii", "replace").split())
+            if lines[-1] == ["end_header"]:
+                break
+        body = f.read()
+    lines = [t for t in lines if t and t[0] != "comment"]
+    counts = {t[1]: int(t[2]) for t in lines if t[0] == "element"}
+    plain = [t[2] for t in lines if t[0] == "property" and t[1] != "list"]
+    if (["format", "binary_little_endian", "1.0"] not in lines or list(counts) != ["vertex", "face"] or
+            plain not in (["x", "y", "z"], ["x", "y", "z", "red", "green", "blue"]) or
+            ["property", "list", "uchar", "int", "vertex_indices"] not in lines):
+        raise ValueError(f"{path}: not a mesh PLY in the layout of save_mesh_ply")
+    fields = [(n, "<f4") for n in "xyz"] + [(n, "u1") for n in plain[3:]]
+    vdt, fdt = np.dtype(fields), np.dtype([("n", "u1"), ("i", "<i4", (3,))])
+    V, T = counts["vertex"], counts["face"]
+    if len(body) != V * vdt.itemsize + T * fdt.itemsize:
+        raise ValueError(f"{path}: {len(body)} bytes of data, the header announces {V * vdt.itemsize + T * fdt.itemsize}")
+    vt = np.frombuffer(body, dtype=vdt, count=V)
+    ft = np.frombuffer(body, dtype=fdt, count=T, offset=V * vdt.itemsize)
+    if T and not (ft["n"] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    vertices = np.stack([vt["x"], vt["y"], vt["z"]], 1).astype(np.float32) if V else np.zeros((0, 3), np.float32)
+    colors = (np.stack([vt[n] for n in plain[3:]], 1) if V else np.zeros((0, 3), np.uint8)) if len(plain) == 6 else None
+    return vertices, ft["i"].astype(np.int32).reshape(T, 3), colors
+
+
 # ------------------------------------------------------------------------------------------- COLMAP sparse models
 _CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5),
                   4: ("OPENCV", 8), 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5),

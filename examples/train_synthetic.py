@@ -17,6 +17,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --mcmc --filter-3d     # ... with the 3D smoothing filter of Mip-Splatting
     python examples/train_synthetic.py --steps 300 --mcmc --distortion 1  # ... with the depth-distortion regulariser on the blending weights
     python examples/train_synthetic.py --steps 300 --mcmc --normal 0.05   # ... with the depth-normal consistency term on the composited normals
+    python examples/train_synthetic.py --steps 300 --mcmc --distortion 0.1 --normal 0.05 --mesh out.ply   # ... and the surface: TSDF fusion + mesh
     python examples/train_synthetic.py --steps 300 --topk                 # ... grown by score to a budget, pruned by contribution
     python examples/train_synthetic.py --steps 200 --absgrad              # ... the published densify / prune on the AbsGS statistic
     python examples/train_synthetic.py --steps 300 --topk --absgrad       # ... the budgeted policy, scored by the AbsGS statistic
@@ -53,7 +54,8 @@ from casualhdrsplat_amd.optim import cloud_param_groups
 from casualhdrsplat_amd.losses import photometric_loss
 from casualhdrsplat_amd.optim import GaussianAdam
 from casualhdrsplat_amd.graphs import GraphedStep
-from casualhdrsplat_amd.rasterizer import DensifyStats, GaussianRasterizer
+from casualhdrsplat_amd.rasterizer import DensifyStats, GaussianRasterizationSettings, GaussianRasterizer
+from casualhdrsplat_amd.tsdf import TSDFVolume
 from casualhdrsplat_amd.vq import dequantize_sh, quantize_sh
 from casualhdrsplat_amd.image_formation import (FrameRasterizers, HDRBlurFormation, ImplicitCRF, TrajectorySpline,
                                                   knots_from_lookat)
@@ -81,7 +83,7 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
         mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False, absgrad=False,
-        bilagrid=False, distort=None, vq=0, distortion=None, normal=None):
+        bilagrid=False, distort=None, vq=0, distortion=None, normal=None, mesh=None):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -143,7 +145,16 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     added to the frame's loss.  With more than one virtual pose per frame this is an APPROXIMATION: the term sees the pose
     average of the composited normals, of the alpha and of the inverse depth, with the mid pose's rotation -- not a term per
     pose.  The history gains `normal`, the mean of the map averaged over the frames.  LAMBDA = 0 computes the map without a
-    gradient: the run to compare with.  Not with graph=True or batch_frames=True (neither delivers the optional outputs)."""
+    gradient: the run to compare with.  Not with graph=True or batch_frames=True (neither delivers the optional outputs).
+    mesh = PATH: after the last step every captured frame is rendered once more SHARP -- one pose, the middle of its exposure
+    window -- with the accumulated opacity and the inverse depth; the frames are fused into a tsdf.TSDFVolume over the cloud's
+    bounds as the frames see it (the 1 % .. 99 % range of the back-projected depth samples plus 5 %, 160 samples along the longest
+    side; the means of an MCMC cloud bound nothing: its transparent Gaussians wander far off), colour from the LDR images, in one
+    integrate call, and the mesh extract_mesh returns is written to PATH (scene_io.save_mesh_ply).  The result gains `mesh`:
+    V, T, the volume's dims and voxel size.  Eager only (not with graph=True: the captured rasterizers return no depth)."""
+    if mesh is not None and graph:
+        raise ValueError("mesh=PATH (--mesh) is not supported together with graph=True (--graph): the surface is fused from the "
+                         "rasterizer's return_alpha / return_invdepth outputs, which the captured step's rasterizers do not deliver")
     if normal is not None and (graph or batch_frames):
         raise ValueError("normal=LAMBDA (--normal) is not supported together with graph=True (--graph) or batch_frames=True "
                          "(--batch-frames): the term needs the rasterizer's return_alpha / return_invdepth outputs, which "
@@ -528,6 +539,49 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
                 sizes = [os.path.getsize(os.path.join(tmp, n)) for n in ("cloud.ply", "cloud.npz")]
         out["vq"] = dict(K=int(vq), P=int(q["means3D"].shape[0]), weighted=weights is not None, psnr_full_vs_quantised_db=psnr,
                          ply_bytes=sizes[0], vq_bytes=sizes[1], sh_codebook=book, sh_codes=codes)
+    if mesh is not None:
+        with torch.no_grad():
+            q = {k: v.detach() for k, v in cur.items()}
+            opac = q["opacities"] if raw else torch.sigmoid(q["opacities"])
+            w2c = model.trajectory.pose_at(model.frame_times.to(model.log_exposure.dtype))      # the mid-exposure pose of every frame
+            full = torch.matmul(model.proj.to(w2c.dtype)[None], w2c)
+            campos = -torch.matmul(w2c[:, :3, :3].transpose(1, 2), w2c[:, :3, 3:])[..., 0]
+            views, projs = w2c.transpose(1, 2).contiguous(), full.transpose(1, 2).contiguous()
+            images, alphas, invdepths = [], [], []
+            for i in range(frames):
+                settings = GaussianRasterizationSettings(
+                    image_height=H, image_width=W, tanfovx=cam.tanfovx, tanfovy=cam.tanfovy, bg=torch.zeros(3, device=dev),
+                    scale_modifier=1.0, viewmatrix=views[i], projmatrix=projs[i], sh_degree=deg, campos=campos[i], prefiltered=False,
+                    debug=False, exposure=torch.exp(model.log_exposure[i]), crf_table=model.crf.table(), crf_range=model.crf.u_range,
+                    viewmatrices=views[i:i + 1], projmatrices=projs[i:i + 1], camposes=campos[i:i + 1], blur_domain=model.blur_domain)
+                rast = GaussianRasterizer(settings, **{**how, "return_alpha": True, "return_invdepth": True},
+                                          **({"filter_3D": filt["filter_3D"]} if filter_3d else {}))
+                res = rast(q["means3D"], torch.zeros_like(q["means3D"]), opac, shs=q["shs"], scales=q["scales"], rotations=q["rotations"])
+                images.append(res[0].reshape(3, H, W))
+                alphas.append(res[-2].reshape(H, W))
+                invdepths.append(res[-1].reshape(H, W))
+            invdepths, alphas, views = torch.stack(invdepths), torch.stack(alphas), views.to(torch.float32)
+            # the bounds of the cloud AS THE FRAMES SEE IT: the depth samples integrate will use, back-projected (the means of an
+            # MCMC cloud do not bound anything: its transparent Gaussians random-walk far from the scene)
+            seen = torch.isfinite(invdepths) & (invdepths > 0) & torch.isfinite(alphas) & (alphas >= 0.5)
+            if not bool(seen.any()):
+                raise RuntimeError("mesh=PATH (--mesh): no pixel of any frame has alpha >= 0.5: the cloud has no surface to fuse")
+            z = torch.where(seen, alphas, torch.ones_like(alphas)) / torch.where(seen, invdepths, torch.ones_like(invdepths))
+            xh = (torch.arange(W, device=dev, dtype=torch.float32) + 0.5 - W / 2) / fx
+            yh = (torch.arange(H, device=dev, dtype=torch.float32) + 0.5 - H / 2) / fy
+            p_cam = torch.stack([z * xh[None, None, :], z * yh[None, :, None], z], dim=-1)             # [frames, H, W, 3]
+            p_world = torch.matmul(p_cam - views[:, None, None, 3, :3], views[:, None, :3, :3].transpose(-1, -2))[seen]
+            p_world = p_world[:: max(1, p_world.shape[0] // 1_000_000)]
+            lo, hi = (torch.quantile(p_world, x, dim=0) for x in (0.01, 0.99))
+            pad = 0.05 * (hi - lo) + 1e-3
+            lo, hi = lo - pad, hi + pad
+            voxel = float((hi - lo).max()) / 159.0
+            volume = TSDFVolume.from_bounds(lo.tolist(), hi.tolist(), voxel, color=True, device=dev)
+            volume.integrate(invdepths, views, fx, fy, alpha=alphas, color=torch.stack(images))
+            vertices, faces, colors = volume.extract_mesh()
+            scene_io.save_mesh_ply(mesh, vertices, faces, colors)
+        out["mesh"] = dict(V=int(vertices.shape[0]), T=int(faces.shape[0]), dims=volume.dims, voxel_size=volume.voxel_size,
+                           observed=int((volume.weight >= 1).sum()), path=mesh)
     if bilagrid:
         out["grids"] = grids.grids.detach()
     if whole:
@@ -592,6 +646,10 @@ def main(argv=None):
                          "0 prints it without adding the term.  With more than one virtual pose per frame this is an approximation: "
                          "the term is applied to the pose average of the composited normals, alpha and inverse depth, with the mid "
                          "pose's rotation.  Eager only: not with --graph or --batch-frames")
+    ap.add_argument("--mesh", type=str, default=None, metavar="PATH",
+                    help="after training, render every captured frame sharp (one pose, mid exposure) with alpha and inverse depth, "
+                         "fuse them into a TSDF volume over the bounds of the cloud as those views see it (tsdf.TSDFVolume) and write the extracted triangle "
+                         "mesh to PATH as PLY; prints V, T and the volume's size.  Eager only (not with --graph)")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
@@ -600,7 +658,7 @@ def main(argv=None):
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
             refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk,
-            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq, distortion=a.distortion, normal=a.normal)
+            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq, distortion=a.distortion, normal=a.normal, mesh=a.mesh)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")
@@ -608,6 +666,10 @@ def main(argv=None):
         print(f"mean distortion map {f['distortion']:.6f} -> {l['distortion']:.6f} (lambda {a.distortion:g})")
     if a.normal is not None:
         print(f"mean normal-consistency map {f['normal']:.6f} -> {l['normal']:.6f} (lambda {a.normal:g})")
+    if a.mesh:
+        m = r["mesh"]
+        print(f"mesh {m['path']}: V {m['V']}, T {m['T']}; volume {m['dims'][0]} x {m['dims'][1]} x {m['dims'][2]} samples of "
+              f"{m['voxel_size']:.5f} ({m['observed']} observed)")
     if a.vq:
         v = r["vq"]
         print(f"vq K {v['K']} ({'weighted by contribution' if v['weighted'] else 'unweighted'}), P {v['P']}: PSNR full vs quantised "

@@ -1476,6 +1476,81 @@ typedef struct hs_gaussian_normals_args {
 HS_API int hs_gaussian_normals(const hs_gaussian_normals_args* args, void* hip_stream);
 HS_API int hs_gaussian_normals_backward(const hs_gaussian_normals_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) TSDF fusion of rendered depth maps and mesh extraction (tsdf.hip): what the
+ * surface regularisers above are for -- depth from all training views fused into a truncated signed distance volume, and a
+ * triangle mesh extracted from it.  No gradients.
+ *
+ * The volume.  tsdf, weight: [nz, ny, nx] fp32; color: [3, nz, ny, nx] fp32 planar or NULL.  Sample (i, j, k) sits at
+ * origin + voxel_size (i, j, k) and has the linear index q = (k ny + j) nx + i.  An empty volume holds tsdf = 1, weight = 0,
+ * color = 0; the caller fills it.
+ *
+ * hs_tsdf_integrate: ONE launch; every sample walks the frames f = 0 .. F-1 in order, so that two calls over frames 0 .. a
+ * and a .. F leave the bits of one call over 0 .. F.  invdepth, alpha: [F, H, W] (what out_invdepth and the alpha output
+ * hold; alpha NULL: 1); frame_color: [F, 3, H, W]; viewmatrices: [F, 4, 4] IN DEVICE MEMORY, world to camera in the
+ * rasterizer's transposed convention (hs_fwd_args.viewmatrices).  The principal point is the centre of the frame.  Per frame:
+ *   (xc, yc, zc) = p V (xc = p.x V[0][0] + p.y V[1][0] + p.z V[2][0] + V[3][0], ...); skipped unless zc > 0;
+ *   u = fx xc / zc + W / 2, v = fy yc / zc + H / 2; skipped unless 0 <= u < W and 0 <= v < H (a NaN skips); the pixel is
+ *   (floor u, floor v) -- the nearest pixel centre;
+ *   the sample d = invdepth, a = alpha of that pixel is VALID when both are finite and > 0 (hs_normal_consistency's rule) and
+ *   a >= min_alpha; skipped unless valid; depth = a / d; skipped unless depth <= max_depth (infinity: no limit);
+ *   sdf = depth - zc; skipped when sdf < -trunc; t = min(1, sdf / trunc);
+ *   tsdf = (tsdf w + t) / (w + 1), every colour channel the same with the frame's colour at that pixel, then w = w + 1.
+ * The fp32 operation order is stated at the top of tsdf.hip and restated by tests/tsdf_reference.py.  A workgroup skips a frame
+ * that its whole brick of samples misses; the test is exact (tsdf.hip), the result the same bits.  Traffic: one read and one
+ * write of tsdf and weight (and color): 16 B per sample, 40 B with colour, whatever F, plus the pixels the volume projects to.
+ *
+ * hs_tsdf_mesh_plan, hs_tsdf_mesh_emit: marching tetrahedra on the lattice.  A sample is OBSERVED when weight >= min_weight and
+ * INSIDE when tsdf < 0 (exactly 0 is outside).  Every cell is cut into the six tetrahedra 000 -> e_a -> e_a + e_b -> 111, one
+ * per permutation (a, b, c) of the axes, in lexicographic order.  Their edges are the translates of the seven directions 100,
+ * 010, 001, 110, 101, 011, 111 (edge numbers 0 .. 6, x first), each owned by its lower end.  An owned edge carries a VERTEX
+ * when both ends are observed and exactly one is inside, at pa + (a / (a - b)) (pb - pa) with a, pa at the owner and b, pb at
+ * the other end; colours interpolate the same way.  The formula depends on the edge alone: the mesh is watertight.  A
+ * tetrahedron emits 0, 1 or 2 TRIANGLES by the signs of its corners, only when all four are observed, wound so that the normal
+ * points to the outside (free space).  Vertices are ordered by (q, edge number), triangles by (q, tetrahedron, position in the
+ * case table of tsdf.hip).  Zero-area triangles (a value of exactly 0) stay; a vertex at the rim of the observed region may
+ * be referenced by no triangle and stays too.
+ *   plan: three launches (count, scan, vertex bases); writes the workspace and totals = {V, T} as two int64 IN DEVICE MEMORY.
+ *         The workspace may hold anything before.
+ *   emit: one launch; n_vertices = V and n_faces = T as read from totals by the caller (the one host read of the feature);
+ *         writes vertices [V, 3] fp32, faces [T, 3] int32 and, for a volume with colour, colors [V, 3] fp32 -- every element.
+ *         Between plan and emit the volume, min_weight and the workspace must not change.  V = T = 0: no launch.
+ * Limits (HS_EINVAL, reported before any HIP call): args non-null; nx, ny, nz >= 2, nx ny nz <= 2^30; origin finite;
+ * voxel_size finite and > 0; tsdf, weight non-null; every pointer given 4-byte aligned (workspace 16, totals 8).
+ * integrate: F >= 1, 1 <= H, W <= 65536, 3 F H W < 2^31; fx, fy, trunc finite and > 0; min_alpha not a NaN; max_depth > 0; invdepth and
+ * viewmatrices non-null; frame_color given exactly when color is.  mesh: min_weight not a NaN; workspace non-null; plan:
+ * totals non-null; emit: 0 <= n_vertices, n_faces < 2^31, vertices / faces non-null when their count is not 0, colors given
+ * exactly when color is.  The caller owns every byte, nothing is allocated, cleared or copied, the work is enqueued on the
+ * caller's stream and nothing synchronises. */
+typedef struct hs_tsdf_args {
+    int32_t nx, ny, nz;           /* the volume */
+    int32_t F, H, W;              /* integrate: the frames */
+    float origin[3];              /* the position of sample (0, 0, 0) */
+    float voxel_size;
+    float trunc;                  /* integrate */
+    float fx, fy;                 /* integrate */
+    float min_alpha, max_depth;   /* integrate */
+    float min_weight;             /* mesh */
+    float* tsdf;                  /* [nz, ny, nx]: read and written by integrate, read by the mesh calls */
+    float* weight;                /* [nz, ny, nx]: likewise */
+    float* color;                 /* [3, nz, ny, nx] likewise, or NULL: a volume without colour */
+    const float* invdepth;        /* [F, H, W] */
+    const float* alpha;           /* [F, H, W], or NULL: 1 */
+    const float* frame_color;     /* [F, 3, H, W]; given exactly when color is */
+    const float* viewmatrices;    /* [F, 4, 4], device memory */
+    void* workspace;              /* mesh: hs_tsdf_mesh_workspace_bytes(nx, ny, nz) bytes, written by plan, read by emit */
+    int64_t* totals;              /* plan: {V, T} written, device memory */
+    int64_t n_vertices, n_faces;  /* emit: V and T of the plan */
+    float* vertices;              /* emit: [V, 3] written */
+    int32_t* faces;               /* emit: [T, 3] written */
+    float* colors;                /* emit: [V, 3] written; given exactly when color is */
+} hs_tsdf_args;
+
+HS_API int hs_tsdf_integrate(const hs_tsdf_args* args, void* hip_stream);
+/* 5 bytes per sample and 16 per 256 samples, rounded to 16.  -1 (HS_EINVAL) outside the limits above.  No HIP call. */
+HS_API int64_t hs_tsdf_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
+HS_API int hs_tsdf_mesh_plan(const hs_tsdf_args* args, void* hip_stream);
+HS_API int hs_tsdf_mesh_emit(const hs_tsdf_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
