@@ -396,9 +396,9 @@ int hs_backward(const hs_bwd_args* a, void* hip_stream) {
     }
     if (a->dims.P == 0) return HS_OK;
     // the CRF gradient's first stage rides at the end of the render backward's launch when both run in this call
-    // (its table of K - 1 64-bit LDS words sits in the kernel's staging area: 9 KB, i.e. up to 1024 knots)
+    // (its table of K - 1 64-bit LDS words sits in the kernel's staging area: about 7.5 KB, i.e. some 900 knots)
     const bool crf_in_tail = HS_TUNE_CRF_IN_RENDER_TAIL && (a->stages & HS_BWD_RENDER) && (a->stages & HS_BWD_CRF) &&
-                             !(a->flags & HS_FLAG_DEBUG) && a->crf_K <= 1024;
+                             !(a->flags & HS_FLAG_DEBUG) && a->crf_K <= render_bwd_tail_max_knots();
     if (a->stages & HS_BWD_RENDER) {
         rc = launch_render_bwd(*a, L, s, nullptr, nullptr, crf_in_tail);
         if (rc) return rc;

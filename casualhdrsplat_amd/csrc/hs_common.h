@@ -95,9 +95,10 @@ int launch_render_fwd(const hs_fwd_args& a, const hs_layout& L, hipStream_t s, u
 int launch_render_bwd(const hs_bwd_args& a, const hs_layout& L, hipStream_t s, unsigned long long* stats = nullptr,
                       unsigned long long* timeline = nullptr, bool crf_in_tail = false);
 int render_stats_count();
+int render_bwd_tail_max_knots();   // `crf_in_tail` needs crf_K <= this (the table sits in the kernel's staging area)
 struct CrfReduce;
 // `defer`: non-null = do not launch the second stage; describe it there for the segmented sum's launch to run.
-// `in_render_tail`: the first stage already ran at the end of the render backward's launch (two-wave workgroups: the partial
+// `in_render_tail`: the first stage already ran at the end of the render backward's launch (2048-pixel blocks: the partial
 // rows are counted accordingly)
 int launch_crf_bwd(const hs_bwd_args& a, const hs_layout& L, hipStream_t s, CrfReduce* defer, bool in_render_tail = false);
 int launch_preprocess_bwd(const hs_bwd_args& a, const hs_layout& L, hipStream_t s, bool segsum, bool project,

@@ -4,9 +4,11 @@
 // CDNA4 design (not a translation of the CUDA 16x16-thread tile).  Measured on MI355X the loops are bound by
 // VALU issue (~4 cycles per wave64 VALU instruction, profiles/r01b_valu_rate.txt), so the design minimises vector
 // instructions per (pixel, Gaussian) pair:
-//  * one 128-thread workgroup (two wave64) per 16x16 binning tile; each wave owns a 16x8 half tile and each lane
+//  * forward: one 128-thread workgroup (two wave64) per 16x16 binning tile; each wave owns a 16x8 half tile and each lane
 //    TWO vertically adjacent pixels, so dx and every per-Gaussian term is shared by the pair and the rest is
-//    packed fp32 (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32);
+//    packed fp32 (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32).  Backward: ONE wave64 per tile, each lane FOUR vertically
+//    adjacent pixels (two packed pairs), so what is paid once per lane and entry -- dx and its terms, the cross-lane
+//    reduction, the store -- is paid once per 256 pixel-entries;
 //  * the tile's sorted instance list is staged 128 entries at a time into LDS (one gather of a 64-byte-aligned record
 //    per thread, the next batch prefetched into registers), the conic pre-scaled by -0.5*log2(e) so the inner
 //    loop is  dx, dy -> two FMAs -> v_exp_f32;
@@ -18,10 +20,11 @@
 //    that the tiles one XCD works on are neighbours and share its L2;
 //  * the forward records which staged entries each lane group of each wave actually took (one byte per sorted pair) and
 //    how many trips each tile cost; the backward's lane groups replay exactly those entries, each from its own list;
-//  * backward: no global atomics.  Per (lane group, Gaussian) nine partial sums are formed in-lane over the pixel
-//    pair, reduced across the 32 lanes of the group by halving steps ordered by price (bank-masked DPP adds first, one
-//    v_permlane16_swap / ds_bpermute step, quad steps last), STORED into the group's own plane of the entry's LDS
-//    record (a (wave, group) visits an entry once: no LDS atomics), the planes added in a fixed order and written as
+//  * backward: no global atomics.  The four 16-lane DPP rows of the wave are its lane groups, each an 8 x 8 block walking
+//    its OWN list of takers (one iteration serves up to four different entries).  Per (lane group, Gaussian) nine partial
+//    sums are formed in-lane over the four pixels, reduced across the 16 lanes of the row by DPP halving steps and two
+//    quad steps (no swap, no LDS crossbar), STORED into the group's own plane of the entry's LDS
+//    record (a group visits an entry once: no LDS atomics), the planes added in a fixed order and written as
 //    ONE record (a 64-byte sector) per (tile, instance) pair at the pair's duplicateWithKeys slot; preprocess-backward
 //    then sums each instance's contiguous slots.  Gradients are bitwise reproducible run to run;
 //  * the backward's launch ends on light tiles taken from a queue: each XCD keeps its strip-ordered tiles except its
@@ -45,6 +48,10 @@ constexpr float kLogEps = 1e-8f;
 // Diagnostic counters of the STATS instantiations (hs_render_stats: bench.py's lane-utilisation / VALU-roofline
 // leg and profiling; never part of a timed or differentiated call).  Each wave keeps its counts in registers and adds
 // them once at the end.
+// The backward runs one wave per tile and counts in HALF trips, the unit of the two-wave kernel it replaces: a trip is one
+// 128-pixel half of the tile (lanes 32h .. 32h + 31) that holds a real entry in an iteration of the replay loop -- an
+// iteration counts 1 or 2 --, binned by the active lanes of that half (the 33-64 bin stays empty); "culled" = staged
+// entries nobody took.
 enum {
     kStBwdTrips = 0,      // (wave, entry) trips of the backward replay loop
     kStBwdEmpty = 1,      // ... in which no lane had an active pixel
@@ -86,94 +93,76 @@ __device__ __forceinline__ float wave_sum_hi(float v) {
     v += dpp<0x143, 0xC>(v);  // row_bcast:31 -> rows 2,3
     return v;
 }
-// ---- the 9 (10) value reduction of the backward replay (over the 32 lanes of a lane group) ----
+// ---- the 9 (10) value reduction of the backward replay (over the 16 lanes of a DPP row = a lane group) ----
 // Every halving step sums TWO registers over one lane bit into ONE register (x's partial sums land in the lanes
-// whose bit is 0, y's in the lanes whose bit is 1), so the register count shrinks 10 -> 5 -> 3 -> 2.  The steps
-// differ in price -- a bank-masked v_add_f32_dpp issues in 4 cycles, a v_permlane16_swap in 8 (plus its add) -- so
-// the cheap in-row steps (lane bits 3 and 2) run FIRST, while there are many registers, and the swap (bit 4) last,
-// on the few that remain.
-__device__ __forceinline__ float halve16(float x, float y) {  // lane bit 4 (x -> even rows, y -> odd rows)
-    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// In-row steps as bank-masked DPP adds (the compiler's DPP combiner only folds full-mask moves, so these are written
-// out).  pair8(x, y): lanes with (lane & 8) == 0 get x[l] + x[l+8], the others y[l] + y[l-8]; pair4 likewise on lane
-// bit 2.  A VALU write followed by a DPP read of the same register needs two wait states (hipcc pads nothing inside
-// asm): the ten inputs are written by ordinary code just before, hence the leading s_nop; inside the block every
-// register is read at least two instructions after it was written.  The trailing s_nop covers the v_permlane16_swap
-// the compiler places behind the block.
-// Out: w0 = {g0, g2, g1, g3} by quad, w1 = {g4, g6, g5, g7} by quad, w2 = {g8, g8, g9, g9} by quad -- each the sum over
-// lane bits 3 and 2, i.e. over the four quads of the row.
+// whose bit is 0, y's in the lanes whose bit is 1), so the register count shrinks 10 -> 5 -> 3; the two quad steps then
+// run on the three registers that remain.  DPP only: a lane group never crosses its row, so the reduction needs neither
+// a v_permlane16_swap (8 issue cycles) nor the LDS crossbar.  The in-row steps are bank-masked DPP adds (the compiler's
+// DPP combiner only folds full-mask moves, so these are written out): lanes with (lane & 4) == 0 get x[l] + x[l+4], the
+// others y[l] + y[l-4]; likewise on lane bit 3.  Lane bit 2 (columns c and c + 4) goes BEFORE lane bit 3 (rows 0..3 and
+// 4..7 of the block): with the lane's own (row 0 + row 1) + (row 2 + row 3) in front and the quad steps behind, a sum
+// over an 8 x 8 block is added up in the order of the two-wave kernel this one replaces (pixel pair, row pairs, column
+// halves, row halves, columns) -- tests/test_gpu_parity.py holds the largest frames within a few per cent of their bars.  A VALU write followed by a DPP read of the same register needs two wait
+// states (hipcc pads nothing inside asm): the inputs are written by ordinary code just before, hence the leading s_nop;
+// inside the block every register is read at least two instructions after it was written (scripts/isa_loop_counts.py
+// checks this on the emitted ISA).
+// Out, in every row, all four lanes of a quad alike:
+//   t0: quads 0..3 = g0, g1, g2, g3      t1: quads 0..3 = g4, g5, g6, g7      t2: quads 0..3 = g8, g9, g8, g9.
 template <bool TEN>
-__device__ __forceinline__ void reduce_in_rows(const float* g, float g9, float& w0, float& w1, float& w2) {
+__device__ __forceinline__ void row_reduce(const float* g, float g9, float& t0, float& t1, float& t2) {
     float z0, z1, z2, z3, z4;
     if constexpr (TEN) {
         asm("s_nop 1\n\t"
-            "v_add_f32_dpp %3, %9, %9 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %3, %8, %8 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %4, %11, %11 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %4, %10, %10 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %5, %13, %13 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %5, %12, %12 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %6, %15, %15 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %6, %14, %14 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %7, %17, %17 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %7, %16, %16 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %0, %4, %4 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-            "v_add_f32_dpp %0, %3, %3 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-            "v_add_f32_dpp %1, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-            "v_add_f32_dpp %1, %5, %5 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-            "v_add_f32_dpp %2, %7, %7 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-            "v_add_f32_dpp %2, %7, %7 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-            "s_nop 1"
-            : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(z0), "=&v"(z1), "=&v"(z2), "=&v"(z3), "=&v"(z4)
+            "v_add_f32_dpp %3, %9, %9 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %3, %8, %8 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %4, %11, %11 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %4, %10, %10 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %5, %13, %13 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %5, %12, %12 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %6, %15, %15 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %6, %14, %14 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %7, %17, %17 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %7, %16, %16 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %0, %4, %4 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_add_f32_dpp %0, %3, %3 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_add_f32_dpp %1, %6, %6 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_add_f32_dpp %1, %5, %5 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_add_f32_dpp %2, %7, %7 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_add_f32_dpp %2, %7, %7 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+            : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(z0), "=&v"(z1), "=&v"(z2), "=&v"(z3), "=&v"(z4)
             : "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]), "v"(g[6]), "v"(g[7]), "v"(g[8]), "v"(g9));
     } else {
-        // nine values: the odd one is summed over bits 3 and 2 by two full-row rotations (every lane gets the total)
+        // nine values: the odd one is summed over bits 2 and 3 by two full-row rotations (every lane gets the total)
         asm("s_nop 1\n\t"
-            "v_add_f32_dpp %3, %9, %9 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %3, %8, %8 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %4, %11, %11 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %4, %10, %10 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %5, %13, %13 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %5, %12, %12 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %6, %15, %15 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
-            "v_add_f32_dpp %6, %14, %14 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
-            "v_add_f32_dpp %7, %16, %16 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
-            "v_add_f32_dpp %0, %4, %4 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-            "v_add_f32_dpp %0, %3, %3 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-            "v_add_f32_dpp %1, %6, %6 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
-            "v_add_f32_dpp %1, %5, %5 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
-            "v_add_f32_dpp %2, %7, %7 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
-            "s_nop 1"
-            : "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(z0), "=&v"(z1), "=&v"(z2), "=&v"(z3), "=&v"(z4)
+            "v_add_f32_dpp %3, %9, %9 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %3, %8, %8 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %4, %11, %11 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %4, %10, %10 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %5, %13, %13 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %5, %12, %12 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %6, %15, %15 row_shr:4 row_mask:0xf bank_mask:0xa\n\t"
+            "v_add_f32_dpp %6, %14, %14 row_shl:4 row_mask:0xf bank_mask:0x5\n\t"
+            "v_add_f32_dpp %7, %16, %16 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %0, %4, %4 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_add_f32_dpp %0, %3, %3 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_add_f32_dpp %1, %6, %6 row_shr:8 row_mask:0xf bank_mask:0xc\n\t"
+            "v_add_f32_dpp %1, %5, %5 row_shl:8 row_mask:0xf bank_mask:0x3\n\t"
+            "v_add_f32_dpp %2, %7, %7 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %1, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %2, %2, %2 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %1, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
+            "v_add_f32_dpp %2, %2, %2 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
+            : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(z0), "=&v"(z1), "=&v"(z2), "=&v"(z3), "=&v"(z4)
             : "v"(g[0]), "v"(g[1]), "v"(g[2]), "v"(g[3]), "v"(g[4]), "v"(g[5]), "v"(g[6]), "v"(g[7]), "v"(g[8]));
     }
-}
-// The two quad steps (lane bits 1 and 0): every lane of a quad ends with the quad's total.
-__device__ __forceinline__ float reduce_in_quads(float t) {
-    asm("s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-        "s_nop 1\n\t"
-        "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
-        : "+v"(t));
-    return t;
-}
-
-// Nine (ten) values reduced over each 32-lane half of the wave separately (the lane groups of the render backward): the
-// in-row steps, then ONE swap step over lane bit 4 for two of the three registers, the third through the LDS crossbar
-// (`xor16_addr` = ((lane ^ 16) << 2): an LDS-pipe instruction plus one vector add instead of copy + swap + add -- the loop
-// is bound by vector issue, the LDS pipe is not), then the quad steps on both results -- lane bit 5 is never crossed.
-// Out, per group (rows 2g and 2g + 1 of the wave), all four lanes of a quad alike:
-//   t0: row 2g, quads 0..3 = g0, g2, g1, g3 ; row 2g + 1, quads 0..3 = g4, g6, g5, g7      t1: every row, quads = g8, g8, g9, g9.
-template <bool TEN>
-__device__ __forceinline__ void group_reduce(const float* g, float g9, int xor16_addr, float& t0, float& t1) {
-    float w0, w1, w2;
-    reduce_in_rows<TEN>(g, g9, w0, w1, w2);
-    const float u0 = halve16(w0, w1);  // even rows: w0 over bit 4, odd rows: w1 over bit 4
-    const float u1 = w2 + __int_as_float(__builtin_amdgcn_ds_bpermute(xor16_addr, __float_as_int(w2)));
-    t0 = reduce_in_quads(u0);
-    t1 = reduce_in_quads(u1);
 }
 
 // number of set bits of a wave-uniform 64-bit mask below this lane
@@ -762,8 +751,11 @@ __global__ void __launch_bounds__(1024) order_tiles_kernel(int nb, int gx, int n
 // ones); the two fields of an interval are turned back into floats and written as the block's partial row.  Quantisation step = 2^-19 of the block's
 // largest |g|, unbiased.  Exposure gradient and the clamped ends of the table: per-thread float sums in pixel order,
 // fixed DPP tree over the wave, the four waves added in wave order.  crf_reduce_kernel adds the blocks in a fixed order.
-// NW waves per workgroup (4: a launch of its own or the segmented sum's; 2: the tail of the render backward's launch, whose
-// workgroups are 128 threads): a workgroup owns NW * 1024 pixels; the partial rows are per workgroup either way.
+// NW waves per workgroup (4: a launch of its own or the segmented sum's): a workgroup owns NW * NH * 1024 pixels; the partial
+// rows are per workgroup either way.  NH > 1 (the tail of the render backward's launch, whose workgroups are ONE wave): the
+// wave takes NH pieces of 1024 pixels one after the other into the same LDS table, standing in for NH waves -- the block scale
+// is taken over all its pixels first, the integer adds commute, and the per-piece float sums are added in piece order, so
+// the partial row has the bits a workgroup of NH waves writes.
 constexpr int kCrfPixPerWave = 1024;
 
 struct CrfGradArgs {
@@ -774,13 +766,16 @@ struct CrfGradArgs {
 
 // (`bxi`, `plane`: which pixel block of which plane this workgroup takes -- blockIdx of the stand-alone launch)
 // `s_tab64`: K - 1 64-bit LDS words (the stand-alone launches' dynamic LDS; a corner of the render backward's staging area)
-template <int NW>
+template <int NW, int NH = 1>
 __device__ __forceinline__ void crf_grad_body(const CrfGradArgs& A, const int bxi, const int plane_in,
                                               unsigned long long* const s_tab64) {
+    static_assert(NH == 1 || NW == 1, "pieces in turn: one-wave workgroups only");
+    constexpr int NP = NW * NH;   // 1024-pixel pieces of the block (one per wave, or NH of the one wave)
+    static_assert(NP == 2 || NP == 4, "the pieces' float sums are added in a stated order");
     const int64_t HW = A.HW; const int N = A.N, flags = A.flags; const float* pose_hdr = A.pose_hdr; Crf crf = A.crf;
     const float* exposure = A.exposure; const float* dL_dcolor = A.dL_dcolor; float* partials = A.partials;
     int* const s_tab32 = reinterpret_cast<int*>(s_tab64);   // K - 1 intervals: two 32-bit fixed-point fields each
-    __shared__ float s_wave[NW][4];
+    __shared__ float s_wave[NP][4];
     __shared__ float s_max[NW];
     const int K = crf.K;
     for (int i = threadIdx.x; i < K - 1; i += NW * 64) s_tab64[i] = 0ull;
@@ -796,86 +791,101 @@ __device__ __forceinline__ void crf_grad_body(const CrfGradArgs& A, const int bx
     const float* t = crf.table + ch * K;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
-    const int64_t i16 = ((int64_t)bxi * (NW * 64) + threadIdx.x) * 16;
-    float Hv[16], g[16];
-    if (i16 + 16 <= HW && (HW & 3) == 0) {
+    float Hv[NH][16], g[NH][16];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 h4 = reinterpret_cast<const float4*>(Hp + i16)[q];
-            const float4 g4 = reinterpret_cast<const float4*>(gp + i16)[q];
-            Hv[4 * q] = h4.x; Hv[4 * q + 1] = h4.y; Hv[4 * q + 2] = h4.z; Hv[4 * q + 3] = h4.w;
-            g[4 * q] = g4.x * gs; g[4 * q + 1] = g4.y * gs; g[4 * q + 2] = g4.z * gs; g[4 * q + 3] = g4.w * gs;
-        }
-    } else {
+    for (int h = 0; h < NH; ++h) {
+        const int64_t i16 = ((int64_t)bxi * (NP * 64) + h * 64 + threadIdx.x) * 16;   // (NH > 1: threadIdx.x is the lane)
+        if (i16 + 16 <= HW && (HW & 3) == 0) {
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const bool ok = i16 + e < HW;
-            Hv[e] = ok ? Hp[i16 + e] : 0.f;
-            g[e] = ok ? gp[i16 + e] * gs : 0.f;
+            for (int q = 0; q < 4; ++q) {
+                const float4 h4 = reinterpret_cast<const float4*>(Hp + i16)[q];
+                const float4 g4 = reinterpret_cast<const float4*>(gp + i16)[q];
+                Hv[h][4 * q] = h4.x; Hv[h][4 * q + 1] = h4.y; Hv[h][4 * q + 2] = h4.z; Hv[h][4 * q + 3] = h4.w;
+                g[h][4 * q] = g4.x * gs; g[h][4 * q + 1] = g4.y * gs; g[h][4 * q + 2] = g4.z * gs; g[h][4 * q + 3] = g4.w * gs;
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const bool ok = i16 + e < HW;
+                Hv[h][e] = ok ? Hp[i16 + e] : 0.f;
+                g[h][e] = ok ? gp[i16 + e] * gs : 0.f;
+            }
         }
     }
     // block maximum of |g| -> fixed-point scale (max is order independent)
     float mx = 0.f;
 #pragma unroll
-    for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fabsf(g[e]));
+    for (int h = 0; h < NH; ++h)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, fabsf(g[h][e]));
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
     if (lane == 0) s_max[wave] = mx;
     __syncthreads();  // also: the table is cleared
-    mx = fmaxf(s_max[0], s_max[1]);
-    if constexpr (NW == 4) mx = fmaxf(mx, fmaxf(s_max[2], s_max[3]));
+    mx = s_max[0];
+    if constexpr (NW >= 2) mx = fmaxf(mx, s_max[1 % NW]);
+    if constexpr (NW == 4) mx = fmaxf(mx, fmaxf(s_max[2 % NW], s_max[3 % NW]));
     // mx = m * 2^x with m in [0.5, 1)  ->  |g| * 2^(19 - x) < 2^19 ; non-finite or zero gradients: scale 1 (sums are
     // zero or garbage-in-garbage-out, as with float adds)
     int xexp = 0;
     if (mx > 0.f && mx < 3.0e38f) (void)frexpf(mx, &xexp);
     const float to_fix = ldexpf(1.f, 19 - xexp), from_fix = ldexpf(1.f, xexp - 19);
 
-    float gexp = 0.f, g_lo = 0.f, g_hi = 0.f;
-    int run = -1;              // knot interval of the pending run (-1: none)
-    float r0 = 0.f, r1 = 0.f;  // pending contributions to table[run], table[run + 1]
-    auto flush = [&]() {
-        // two 32-bit integer LDS atomics (a CU retires them several times faster than one 64-bit or float atomic,
-        // profiles/README.md "lane groups"); 19 bits below 2^31 leave room for the block's 4096 addends per field
-        atomicAdd(&s_tab32[2 * run], __float2int_rn(r0 * to_fix));
-        atomicAdd(&s_tab32[2 * run + 1], __float2int_rn(r1 * to_fix));
-    };
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        int idx; float f, xv; bool in;
-        crf_locate(crf, Hv[e], idx, f, xv, in);
-        // pixels clamped to an end of the table (black / saturated regions) are summed per thread
-        const bool lo = idx == 0 && f == 0.f, hi = idx == K - 2 && f == 1.f;
-        g_lo += lo ? g[e] : 0.f;
-        g_hi += hi ? g[e] : 0.f;
-        if (!lo && !hi) {
-            if (idx != run) {
-                if (run >= 0) flush();
-                run = idx; r0 = 0.f; r1 = 0.f;
+    for (int h = 0; h < NH; ++h) {
+        float gexp = 0.f, g_lo = 0.f, g_hi = 0.f;
+        int run = -1;              // knot interval of the pending run (-1: none)
+        float r0 = 0.f, r1 = 0.f;  // pending contributions to table[run], table[run + 1]
+        auto flush = [&]() {
+            // two 32-bit integer LDS atomics (a CU retires them several times faster than one 64-bit or float atomic,
+            // profiles/README.md "lane groups"); 19 bits below 2^31 leave room for the block's 4096 addends per field
+            atomicAdd(&s_tab32[2 * run], __float2int_rn(r0 * to_fix));
+            atomicAdd(&s_tab32[2 * run + 1], __float2int_rn(r1 * to_fix));
+        };
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            int idx; float f, xv; bool in;
+            crf_locate(crf, Hv[h][e], idx, f, xv, in);
+            // pixels clamped to an end of the table (black / saturated regions) are summed per thread
+            const bool lo = idx == 0 && f == 0.f, hi = idx == K - 2 && f == 1.f;
+            g_lo += lo ? g[h][e] : 0.f;
+            g_hi += hi ? g[h][e] : 0.f;
+            if (!lo && !hi) {
+                if (idx != run) {
+                    if (run >= 0) flush();
+                    run = idx; r0 = 0.f; r1 = 0.f;
+                }
+                r0 += (1.f - f) * g[h][e];
+                r1 += f * g[h][e];
             }
-            r0 += (1.f - f) * g[e];
-            r1 += f * g[e];
+            if (in) gexp += g[h][e] * (t[idx + 1] - t[idx]) * scale * __builtin_amdgcn_rcpf(xv) * Hv[h][e];
         }
-        if (in) gexp += g[e] * (t[idx + 1] - t[idx]) * scale * __builtin_amdgcn_rcpf(xv) * Hv[e];
+        if (run >= 0) flush();
+        gexp = wave_sum_hi(gexp);
+        g_lo = wave_sum_hi(g_lo);
+        g_hi = wave_sum_hi(g_hi);
+        if (lane == 63) { s_wave[wave + h][0] = gexp; s_wave[wave + h][1] = g_lo; s_wave[wave + h][2] = g_hi; }   // (NH > 1: wave is 0)
     }
-    if (run >= 0) flush();
-    gexp = wave_sum_hi(gexp);
-    g_lo = wave_sum_hi(g_lo);
-    g_hi = wave_sum_hi(g_hi);
-    if (lane == 63) { s_wave[wave][0] = gexp; s_wave[wave][1] = g_lo; s_wave[wave][2] = g_hi; }
     __syncthreads();
+    // the pieces' sums, in piece order
+    auto pieces = [&](int c) {
+        float v = s_wave[0][c] + s_wave[1][c];
+        if constexpr (NP == 4) v = (v + s_wave[2 % NP][c]) + s_wave[3 % NP][c];
+        return v;
+    };
     // partial row of this block: K knots of its channel + its exposure term
     float* dst = partials + ((int64_t)plane_in * A.bx + bxi) * (K + 1);
     for (int k = threadIdx.x; k <= K; k += NW * 64) {
         float v;
         if (k == K) {
-            v = NW == 4 ? ((s_wave[0][0] + s_wave[1][0]) + s_wave[2 % NW][0]) + s_wave[3 % NW][0] : s_wave[0][0] + s_wave[1][0];
+            v = pieces(0);
         } else {
             long long acc = 0;  // field 0 of interval k + field 1 of interval k - 1
             if (k < K - 1) acc += (long long)s_tab32[2 * k];
             if (k > 0) acc += (long long)s_tab32[2 * (k - 1) + 1];
             v = (float)acc * from_fix;
-            if (k == 0) v += NW == 4 ? ((s_wave[0][1] + s_wave[1][1]) + s_wave[2 % NW][1]) + s_wave[3 % NW][1] : s_wave[0][1] + s_wave[1][1];
-            if (k == K - 1) v += NW == 4 ? ((s_wave[0][2] + s_wave[1][2]) + s_wave[2 % NW][2]) + s_wave[3 % NW][2] : s_wave[0][2] + s_wave[1][2];
+            if (k == 0) v += pieces(1);
+            if (k == K - 1) v += pieces(2);
         }
         dst[k] = v;
     }
@@ -993,36 +1003,54 @@ __device__ __forceinline__ void step_bwd_pair(PairB& s, bool act0, bool act1, f2
 // LDS record of one staged entry in the backward: the twelve floats of its render record followed by four planes of
 // reduced partial sums, so ONE per-entry byte offset (what the per-group lists store) addresses everything.
 //   [0..3] x, y, A2, B2   [4..7] C2, opacity, r, g   [8..11] b, 1/depth (DEPTH) or depth, radius, pair-slot start
-//   [12 + NV * (2g + w) ...): the NV = nine (ten) sums of the entry over the pixels of lane group g of wave w.  A (wave,
-//   group) visits an entry at most once, so it STORES its totals (no LDS atomics: a CU retires only ~0.27 lanes of
-//   ds_add_f32 per clock, which is what the twenty adding lanes per trip of the two-group walk ran into --
+//   [12 + NV * (2g + w) ...): the NV = nine (ten) sums of the entry over the pixels of the 8 x 8 block (g, w) of the tile
+//   (columns 8g .., rows 8w ..: the lane group that walks bit 2g + w of the forward's activity byte).  A group visits an
+//   entry at most once, so it STORES its totals (no LDS atomics: a CU retires only ~0.27 lanes of ds_add_f32 per clock --
 //   profiles/README.md); planes nobody wrote are skipped at write-out by the entry's activity bits, the others are added
 //   in plane order: bitwise reproducible.
 constexpr int kTailPct = 8;           // share of the tiles handed out by the queue (see the kernel)
 constexpr int kAccF = 12;             // first float of the sums
-// staged entries per batch (<= 64: the lists are built from one ballot per group).  52 entries = 10.8 KB of LDS per
-// workgroup, which -- with the kernel held to 72 registers (amdgpu_waves_per_eu 7, no spill in the loop) -- lets seven
-// waves per SIMD stay resident.  Measured at c3 (whole step, ms): 64 entries / six waves 1.197, 52 / seven 1.179, 48 / seven
-// 1.191, 56 / seven 1.213, 40 / eight (64 registers, spills) 1.209; 96 / 128 entries (four / three waves): 0.473 / 0.504 ms
-// for the kernel against 0.468.
-constexpr int kBwdKB = 52;
+constexpr int kBwdWave = 64;          // threads per workgroup of the render backward: ONE wave, which owns a whole tile
+// Staged entries per batch (<= 64: one entry per lane, the lists are built from one ballot per group) and resident waves
+// per SIMD the register allocation aims at.  A workgroup is one wave, so its LDS -- (KB + 1) records of 192 bytes, the
+// four lists -- is paid per WAVE: the two have to be chosen together (profiles/README.md, "one wave per tile", has the
+// sweep).
+#ifndef HS_TUNE_BWD_KB
+#define HS_TUNE_BWD_KB 48
+#endif
+#ifndef HS_TUNE_BWD_WAVES
+#define HS_TUNE_BWD_WAVES 4
+#endif
+constexpr int kBwdKB = HS_TUNE_BWD_KB;
+// floats of the kernel's staging area: the batch's records and the sentinel -- or, if that is more, the seven planes of 256
+// pixels the prologue's re-deal borrows.  The CRF-gradient tail workgroups keep their table of K - 1 64-bit words in it.
+constexpr int bwd_stage_floats(int ent_f) { return (kBwdKB + 1) * ent_f > 7 * 256 ? (kBwdKB + 1) * ent_f : 7 * 256; }
 
+// Lane -> pixels of the render backward.  The wave owns the whole 16 x 16 tile at (sx, sy); its four 16-lane DPP rows are
+// the four lane groups, row `blk` = g + 2w owning the 8 x 8 block (g, w) as 8 columns x 2 row quads: the lane owns the
+// FOUR vertically adjacent pixels (px, py0 .. py0 + 3) -- two packed pairs that share px, hence dx and every term of it.
+__device__ __forceinline__ void lane_pixels4(int lane, int sx, int sy, int& px, int& py0) {
+    const int blk = lane >> 4;
+    px = sx + 8 * (blk & 1) + (lane & 7);
+    py0 = sy + 8 * (blk >> 1) + 4 * ((lane >> 3) & 1);
+}
 
 template <bool DEPTH, bool STATS>
-__global__ void __launch_bounds__(kBatch) __attribute__((amdgpu_waves_per_eu((DEPTH || STATS) ? 1 : 7)))
+__global__ void __launch_bounds__(kBwdWave) __attribute__((amdgpu_waves_per_eu((DEPTH || STATS) ? 1 : HS_TUNE_BWD_WAVES)))
 render_bwd_kernel(RenderBwd p) {
-    constexpr int KB = kBwdKB;              // staged entries per batch (<= threads per workgroup)
+    constexpr int KB = kBwdKB;              // staged entries per batch (<= lanes of the wave)
     constexpr int NV = DEPTH ? 10 : 9;      // reduced values per (tile, entry): nine published sums (+ d inverse depth)
     constexpr int kEntF = kAccF + 4 * NV;   // floats per LDS entry record: 48 (192 bytes) / 52 (208 bytes)
     constexpr int kEntB = kEntF * 4;        // ... a multiple of 16 bytes either way: every record stays 16-byte aligned
     static_assert(kEntB % 16 == 0, "LDS entry records must stay 16-byte aligned");
+    static_assert(KB <= kBwdWave, "one staged entry per lane, one ballot per list");
     constexpr int kSentinel = KB * kEntB;   // byte offset of the record no pixel takes (opacity 0)
     constexpr int kListLen = KB + 8;        // the read-ahead of the slot behind the last one stays inside the array
-    __shared__ __attribute__((aligned(16))) float s_ent[(KB + 1) * kEntF];   // record KB: the sentinel
-    static_assert(KB * kEntF >= 2 * 7 * 128, "the pixel-state re-deal of the prologue borrows the staging area below the sentinel");
-    __shared__ uint16_t s_list[2][2][kListLen];   // [wave][lane group]: byte offsets of the group's takers, back to front
-    __shared__ uint8_t s_actb[kBatch];      // activity byte of each staged entry (bit 2g + w: group g of wave w took it)
-    __shared__ uint32_t s_max[2];
+    // the pixel-state re-deal of the prologue borrows the staging area: seven planes of 256 pixels (it may run over the
+    // sentinel record, which is therefore written after it, once per tile)
+    constexpr int kStageF = bwd_stage_floats(kEntF);
+    __shared__ __attribute__((aligned(16))) float s_ent[kStageF];   // record KB: the sentinel
+    __shared__ uint16_t s_list[4][kListLen];   // [lane group]: byte offsets of the group's takers, back to front
 
     // The last kTailPct per cent of the tiles are not bound to a workgroup (hence, through blockIdx, to an XCD): the
     // workgroups behind the static part take them from a queue, one after the other, until it is empty, so an XCD that
@@ -1031,7 +1059,7 @@ render_bwd_kernel(RenderBwd p) {
     // fetches in total and one failing fetch each, and the very last of those 2 n_tail fetches writes the zero back.
     // Measured at c3: -3 % on this kernel at 8 %, the same at 4 and 12 %, nothing at 25 %; the forward LOSES 2 % with
     // the same queue and keeps its static map.
-    __shared__ uint32_t s_q;
+    const int lane = threadIdx.x;
     if constexpr (!STATS) {
         // Workgroups behind the tiles' (round 5): the first stage of the CRF-table / exposure gradient -- independent of this
         // kernel's results, bound by LDS atomics -- handed out by the dispatcher only after every tile has a workgroup, i.e.
@@ -1039,125 +1067,121 @@ render_bwd_kernel(RenderBwd p) {
         // box: a launch of its own 1.1239 ms per step; its workgroups interleaved with the segmented sum's in one launch
         // 1.1145 (all first 1.1153, all last 1.1224); here 1.097 (c4: 7.39 -> 7.32).  A side stream for the same kernel
         // measured noise three times (rounds 1, 3, 4): what helps is WHEN its workgroups are dispatched, not the queue.
+        // A tail workgroup is one wave like the others and takes its 2048-pixel block in two pieces.
         if ((int)blockIdx.x >= p.grid_tiles) {
             const int qd = (int)blockIdx.x - p.grid_tiles;
-            crf_grad_body<2>(p.crf_tail, qd % p.crf_tail.bx, qd / p.crf_tail.bx, reinterpret_cast<unsigned long long*>(s_ent));
+            crf_grad_body<1, 2>(p.crf_tail, qd % p.crf_tail.bx, qd / p.crf_tail.bx, reinterpret_cast<unsigned long long*>(s_ent));
             return;
         }
     }
     const int n_tail = (int)((int64_t)p.grid_tiles * kTailPct / 100);
     const int n_static = p.grid_tiles - n_tail;
-    if (threadIdx.x < kAccF) s_ent[KB * kEntF + threadIdx.x] = 0.f;   // the sentinel record (ordered by the barriers below)
+    // The wave shares its LDS with nobody: the __syncthreads() below are barriers of one wave (no s_barrier is emitted for a
+    // workgroup that fits a wave) -- they state the order of LDS stores and loads of DIFFERENT lanes to the compiler.
     for (;;) {
     int bidx = blockIdx.x;
     if ((int)blockIdx.x >= n_static) {
-        __syncthreads();   // the previous tile of this worker is finished by every thread
-        if (threadIdx.x == 0) {
-            const uint32_t q = atomicAdd(p.queue, 1u);
+        uint32_t q = 0;
+        if (lane == 0) {
+            q = atomicAdd(p.queue, 1u);
             if (q == 2u * (uint32_t)n_tail - 1u) atomicExch(p.queue, 0u);
-            s_q = q;
         }
-        __syncthreads();
-        if (s_q >= (uint32_t)n_tail) return;
-        bidx = n_static + (int)s_q;
+        q = __builtin_amdgcn_readfirstlane(q);
+        if (q >= (uint32_t)n_tail) return;
+        bidx = n_static + (int)q;
     }
     const int vt = p.tile_order ? (int)p.tile_order[bidx] : xcd_strip_tile(bidx, p.grid_tiles, p.gx);
     const int pose = vt / p.ntiles;
     const int tile = vt - pose * p.ntiles;
     const int tx = tile % p.gx, ty = tile / p.gx;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int grp = lane >> 5;               // lane group: the 8 x 8 block of columns 8 grp .. 8 grp + 7 of the half tile
-    const int sx = tx * kTile, sy = ty * kTile + wave * 8;
+    const int blk = lane >> 4;               // lane group = DPP row: the 8 x 8 block (blk & 1, blk >> 1) of the tile
+    const int plane = 2 * (blk & 1) + (blk >> 1);   // ... whose takers are bit 2g + w of the activity bytes, sums in plane 2g + w
+    const int sx = tx * kTile, sy = ty * kTile;
     int px, py0;
-    lane_pixels(lane, sx, sy, px, py0);
-    const int py1 = py0 + 1;
+    lane_pixels4(lane, sx, sy, px, py0);
     const float pxf = (float)px;
-    const f2 pyf = {(float)py0, (float)py1};
+    const f2 pyfA = {(float)py0, (float)(py0 + 1)}, pyfB = {(float)(py0 + 2), (float)(py0 + 3)};
 
     unsigned long long t_start = 0;
     if constexpr (STATS) t_start = wall_clock64();
     const uint2 range = p.ranges[vt];
 
-    // The pixel state is LOADED row-major (lane = column + 16 x row pair: every 16-lane quarter of a load instruction reads
-    // one whole 64-byte row segment) and re-dealt through LDS to the 8 x 8-block mapping of the replay -- the mirror image of
-    // the forward's store path; loaded in the block mapping, each row segment is fetched in two 32-byte pieces by two
-    // different quarters.  The staging area is free here: the previous tile of a queue worker ended behind a barrier, and
-    // the first batch below starts behind one.  Seven planes of 128 pixels per wave, wave-private (LDS accesses of a wave
-    // complete in order: no barrier).
-    PixB s0, s1;
+    // The pixel state is LOADED row-major (lane = column + 16 x (row mod 4): every 16-lane quarter of a load instruction
+    // reads one whole 64-byte row segment) and re-dealt through LDS to the 8 x 8-block mapping of the replay -- the mirror
+    // image of the forward's store path; loaded in the block mapping, each row segment is fetched in two 32-byte pieces by
+    // two different quarters.  The staging area is free here: the previous tile of a queue worker is written out.
+    PairB psA, psB;
+    uint32_t last0, last1, last2, last3;
     {
-        const int qx = sx + (lane & 15), qy0 = sy + 2 * (lane >> 4);
-        PixB t0, t1;
+        __syncthreads();   // the previous tile's write-out has read its records
+        const int qc = lane & 15, qr = lane >> 4;
         const int frame = p.F > 1 ? pose / p.N : 0;   // (uniform; once per tile, in the prologue)
-        load_pixel_bwd(p, t0, qx < p.W && qy0 < p.H, pose, frame, qx, qy0);
-        load_pixel_bwd(p, t1, qx < p.W && qy0 + 1 < p.H, pose, frame, qx, qy0 + 1);
-        float* const o = s_ent + wave * (7 * 128);
-        const int r0 = (qy0 - sy) * 16 + (lane & 15), r1 = r0 + 16;
-        o[r0] = t0.T; o[r1] = t1.T;
-        o[128 + r0] = t0.dL0; o[128 + r1] = t1.dL0;
-        o[256 + r0] = t0.dL1; o[256 + r1] = t1.dL1;
-        o[384 + r0] = t0.dL2; o[384 + r1] = t1.dL2;
-        o[512 + r0] = t0.q; o[512 + r1] = t1.q;
-        o[640 + r0] = t0.dLd; o[640 + r1] = t1.dLd;
-        o[768 + r0] = __uint_as_float(t0.last); o[768 + r1] = __uint_as_float(t1.last);
-        // the reads below take values OTHER lanes of this wave wrote: say so to the compiler (a wavefront-scope release
-        // fence + a wave barrier: no instruction is emitted, the LDS operations of a wave complete in order anyway, but
-        // the order of the stores and the loads is now a stated contract instead of an alias-analysis accident)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const int p0 = (py0 - sy) * 16 + (px - sx), p1 = p0 + 16;
-        s0.T = o[p0]; s0.dL0 = o[128 + p0]; s0.dL1 = o[256 + p0]; s0.dL2 = o[384 + p0]; s0.q = o[512 + p0];
-        s0.dLd = o[640 + p0]; s0.last = __float_as_uint(o[768 + p0]);
-        s1.T = o[p1]; s1.dL0 = o[128 + p1]; s1.dL1 = o[256 + p1]; s1.dL2 = o[384 + p1]; s1.q = o[512 + p1];
-        s1.dLd = o[640 + p1]; s1.last = __float_as_uint(o[768 + p1]);
+        float* const o = s_ent;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int row = qr + 4 * k;
+            PixB t;
+            load_pixel_bwd(p, t, sx + qc < p.W && sy + row < p.H, pose, frame, sx + qc, sy + row);
+            const int r = row * 16 + qc;
+            o[r] = t.T; o[256 + r] = t.dL0; o[512 + r] = t.dL1; o[768 + r] = t.dL2; o[1024 + r] = t.q;
+            o[1280 + r] = t.dLd; o[1536 + r] = __uint_as_float(t.last);
+        }
+        __syncthreads();   // the reads below take values OTHER lanes wrote
+        const float* const m = o + (py0 - sy) * 16 + (px - sx);   // this lane's four pixels: m[0], m[16], m[32], m[48] of a plane
+        psA.T = f2{m[0], m[16]};                  psB.T = f2{m[32], m[48]};
+        psA.dL0 = f2{m[256], m[256 + 16]};        psB.dL0 = f2{m[256 + 32], m[256 + 48]};
+        psA.dL1 = f2{m[512], m[512 + 16]};        psB.dL1 = f2{m[512 + 32], m[512 + 48]};
+        psA.dL2 = f2{m[768], m[768 + 16]};        psB.dL2 = f2{m[768 + 32], m[768 + 48]};
+        psA.q = f2{m[1024], m[1024 + 16]};        psB.q = f2{m[1024 + 32], m[1024 + 48]};
+        psA.dLd = f2{m[1280], m[1280 + 16]};      psB.dLd = f2{m[1280 + 32], m[1280 + 48]};
+        last0 = __float_as_uint(m[1536]); last1 = __float_as_uint(m[1536 + 16]);
+        last2 = __float_as_uint(m[1536 + 32]); last3 = __float_as_uint(m[1536 + 48]);
+        __syncthreads();   // ... and are done before the sentinel and the first batch overwrite them
+        if (lane < kAccF) s_ent[KB * kEntF + lane] = 0.f;   // the sentinel record (ordered by the batch loop's barriers)
     }
-    PairB ps = pack_pair(s0, s1);
 
-    const uint32_t wave_max = wave_max_u32(max(s0.last, s1.last));
-    if (lane == 0) s_max[wave] = wave_max;
-    __syncthreads();
-    const int n_proc = (int)max(s_max[0], s_max[1]);
+    const int n_proc = (int)__builtin_amdgcn_readfirstlane(wave_max_u32(max(max(last0, last1), max(last2, last3))));
 
-    // Which of its group's totals this lane adds to the entry's sums after group_reduce (see there), as a byte offset
-    // inside the entry record (-1: none), and from which of the two result registers: the quad leaders of the group's two
-    // rows carry t0 (eight sums), the second lanes of quads 0 and 2 of its first row carry t1 (the ninth and tenth).
+    // Which of its group's totals this lane stores into the entry's record after row_reduce (see there), as a byte offset
+    // inside the record (-1: none), and from which of the three result registers: lane j of quad k of the row carries
+    // t0 (j = 0: sums 0..3), t1 (j = 1: sums 4..7) or t2 (j = 2, quads 0 and 2: the ninth and tenth).
     int red_off = -1;
-    const bool red_t0 = (lane & 3) == 0;
+    const int red_j = lane & 3;
     {
-        const int row = lane >> 4, k = (lane & 15) >> 2;
-        constexpr int kOrd[4] = {0, 2, 1, 3};
-        if ((lane & 3) == 0) red_off = ((row & 1) ? 4 : 0) + kOrd[k];
-        else if ((lane & 3) == 1 && !(row & 1) && k == 0) red_off = 8;
-        else if (DEPTH && (lane & 3) == 1 && !(row & 1) && k == 2) red_off = 9;
-        if (red_off >= 0) red_off = (kAccF + NV * (2 * grp + wave) + red_off) * 4;
+        const int k = (lane & 15) >> 2;
+        if (red_j == 0) red_off = k;
+        else if (red_j == 1) red_off = 4 + k;
+        else if (red_j == 2 && k == 0) red_off = 8;
+        else if (DEPTH && red_j == 2 && k == 1) red_off = 9;
+        if (red_off >= 0) red_off = (kAccF + NV * plane + red_off) * 4;
     }
-    const int xor16_addr = (lane ^ 16) << 2;
     char* const ent = reinterpret_cast<char*>(s_ent);
-    float* const my_ent = s_ent + threadIdx.x * kEntF;
-    const uint16_t* const my_list = s_list[wave][grp];
+    float* const my_ent = s_ent + lane * kEntF;   // (dereferenced by lanes < KB only)
+    const uint16_t* const my_list = s_list[blk];
     WaveStats ws;
     if constexpr (STATS) ws.clear();
     const int nb = (n_proc + KB - 1) / KB;
-    // only the instance id of the NEXT batch is prefetched (one register); its record is gathered at the
-    // top of the batch -- keeping the three float4 in registers across the replay loop costs a wave of occupancy
-    // The forward left one activity byte per sorted pair (bit 2g + w: some pixel of lane group g of wave w took the
-    // entry).  An entry nobody took is neither gathered nor written out; the two 32-lane groups of a wave each walk
-    // exactly their own takers, so one trip of the loop serves up to two different entries, and no trip is empty.
+    // The forward left one activity byte per sorted pair (bit 2g + w: some pixel of the 8 x 8 block (g, w) took the
+    // entry).  An entry nobody took is neither gathered nor written out; the four 16-lane groups of the wave each walk
+    // exactly their own takers, so one iteration of the loop serves up to four different entries.
+    // Only the instance id and the activity byte of the NEXT batch are prefetched (two registers); its records are gathered
+    // at the top of the batch.  (Gathering the records a batch ahead as well -- three float4 per lane held across the replay
+    // loop, 111 registers -- measured the same: 0.379 / 0.383 ms against 0.385 / 0.383 at c3.)
     uint32_t id_next = 0, act_next = 0;
     if (nb > 0) {
         const int base = (nb - 1) * KB;
-        if ((int)threadIdx.x < n_proc - base) {
-            id_next = p.point_list[range.x + base + threadIdx.x];
-            act_next = p.pair_act[(int64_t)range.x + base + threadIdx.x];
+        if (lane < n_proc - base) {
+            id_next = p.point_list[range.x + base + lane];
+            act_next = p.pair_act[(int64_t)range.x + base + lane];
         }
     }
     for (int bi = nb - 1; bi >= 0; --bi) {
         const int base = bi * KB;
         const int cnt = min(KB, n_proc - base);
-        if constexpr (STATS) { if (wave == 0) { ws.v[kStBwdStaged] += cnt; ws.v[kStBwdBatches] += 1; } }
+        if constexpr (STATS) { ws.v[kStBwdStaged] += cnt; ws.v[kStBwdBatches] += 1; }
         __syncthreads();  // previous batch's write-out finished
-        const bool taken = (int)threadIdx.x < cnt && act_next != 0;
-        s_actb[threadIdx.x] = (uint8_t)((int)threadIdx.x < cnt ? act_next : 0u);
+        const uint32_t act = lane < cnt ? act_next : 0u;   // activity byte of this lane's staged entry
+        const bool taken = act != 0;
         if (taken) {
             const float4* r = p.rec + kRecF4 * (int64_t)id_next;
             float4 ra = r[0], rb = r[1];
@@ -1168,96 +1192,108 @@ render_bwd_kernel(RenderBwd p) {
             reinterpret_cast<float4*>(my_ent)[1] = rb;
             reinterpret_cast<float4*>(my_ent)[2] = rc;
         }
-        if (bi > 0 && (int)threadIdx.x < KB) {  // batches below the top are full
-            id_next = p.point_list[range.x + base - KB + threadIdx.x];
-            act_next = p.pair_act[(int64_t)range.x + base - KB + threadIdx.x];
+        if (bi > 0 && lane < KB) {  // batches below the top are full
+            id_next = p.point_list[range.x + base - KB + lane];
+            act_next = p.pair_act[(int64_t)range.x + base - KB + lane];
         }
-        __syncthreads();
         {
-            // The two lists of this wave: group g's takers among the staged entries (bit 2g + wave of the activity bytes),
-            // back to front, then sentinels up to the longer list's length.  Wave-private LDS rows: no barrier needed.
+            // The four lists: group (g, w)'s takers among the staged entries (bit 2g + w of the activity bytes), back to
+            // front, then sentinels up to the longest list's length.
             int maxn = 0;
+            [[maybe_unused]] int n_half[2] = {0, 0};   // per 128-pixel half of the tile (rows 8w ..): its longer list
 #pragma unroll
-            for (int g = 0; g < 2; ++g) {
-                const uint32_t gbit = 1u << (2 * g + wave);
-                uint16_t* lst = s_list[wave][g];
-                int n_g = 0;
-#pragma unroll
-                for (int k = (KB + 63) / 64 - 1; k >= 0; --k) {   // upper half of the batch first: it is deeper
-                    const uint64_t m = __ballot((s_actb[k * 64 + lane] & gbit) != 0);
-                    const int c = __popcll(m);
-                    if ((m >> lane) & 1ull) lst[n_g + c - 1 - mask_prefix(m)] = (uint16_t)((k * 64 + lane) * kEntB);
-                    n_g += c;
-                }
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t gbit = 1u << (2 * (b & 1) + (b >> 1));
+                uint16_t* lst = s_list[b];
+                const uint64_t m = __ballot((act & gbit) != 0);
+                const int c = __popcll(m);
+                if ((m >> lane) & 1ull) lst[c - 1 - mask_prefix(m)] = (uint16_t)(lane * kEntB);
 #pragma unroll
                 for (int t = lane; t < kListLen; t += 64)
-                    if (t >= n_g) lst[t] = (uint16_t)kSentinel;
-                maxn = max(maxn, n_g);
+                    if (t >= c) lst[t] = (uint16_t)kSentinel;
+                maxn = max(maxn, c);
+                n_half[b >> 1] = max(n_half[b >> 1], c);
             }
-            if constexpr (STATS) {
-                const uint32_t wbits = 5u << wave;
-                uint32_t mine = 0;
-#pragma unroll
-                for (int k = 0; k < (KB + 63) / 64; ++k) mine += __popcll(__ballot((s_actb[k * 64 + lane] & wbits) != 0));
-                ws.v[kStBwdCulled] += (uint32_t)cnt - mine;
-            }
-            // a pixel takes part in entry j of this batch iff base + j < last, i.e. iff j * 128 < (last - base) * 128 (the
+            if constexpr (STATS) ws.v[kStBwdCulled] += (uint32_t)cnt - (uint32_t)__popcll(__ballot(taken));
+            __syncthreads();  // staged, and the lists are written
+            // a pixel takes part in entry j of this batch iff base + j < last, i.e. iff j * 192 < (last - base) * 192 (the
             // sentinel passes this test for pixels that reach past the batch: its opacity 0 is what keeps it out)
-            const int lim0 = ((int)s0.last - base) * kEntB, lim1 = ((int)s1.last - base) * kEntB;
+            const int lim0 = ((int)last0 - base) * kEntB, lim1 = ((int)last1 - base) * kEntB;
+            const int lim2 = ((int)last2 - base) * kEntB, lim3 = ((int)last3 - base) * kEntB;
             int jb = (int)my_list[0];
-            for (int ti = 0; ti < maxn; ++ti) {
-                // next trip's entry, read a trip ahead -- and made a full register: carried as 16 bits it is masked again every
-                // trip.  (Two trips per loop body, to drop the copy that hands it on: the compiler rolls them back into one
-                // body with seven more scalar instructions per trip -- 75 + 15 against 76 + 8 -- so the copy stays.)
+            const int n_it = __builtin_amdgcn_readfirstlane(maxn);   // (uniform by construction; keeps the loop count scalar)
+            for (int ti = 0; ti < n_it; ++ti) {
+                // next iteration's entry, read an iteration ahead -- and made a full register: carried as 16 bits it is
+                // masked again every time
                 int jn = (int)my_list[ti + 1];
                 asm("" : "+v"(jn));
-                const float4 a = *reinterpret_cast<const float4*>(ent + jb);   // (two addresses per wave: one per group)
+                const float4 a = *reinterpret_cast<const float4*>(ent + jb);   // (four addresses per wave: one per group)
                 const float4 b = *reinterpret_cast<const float4*>(ent + jb + 16);
                 const float2 c = *reinterpret_cast<const float2*>(ent + jb + 32);
                 const float cb = c.x;
                 const float invd = DEPTH ? c.y : 0.f;  // staged as 1 / depth in DEPTH kernels
+                // once per lane: dx and its terms are shared by the four pixels
                 const float dx = a.x - pxf;
-                const f2 dy = a.y - pyf;
+                const f2 dyA = a.y - pyfA, dyB = a.y - pyfB;
                 const float t = a.z * dx * dx, u = a.w * dx;
-                const f2 pw = dy * (b.x * dy + u) + t;
-                const float G0 = hs_exp2(pw.x), G1 = hs_exp2(pw.y);
+                const f2 pwA = dyA * (b.x * dyA + u) + t, pwB = dyB * (b.x * dyB + u) + t;
+                const float G0 = hs_exp2(pwA.x), G1 = hs_exp2(pwA.y), G2 = hs_exp2(pwB.x), G3 = hs_exp2(pwB.y);
                 const float al0 = fminf(kAlphaMax, b.y * G0), al1 = fminf(kAlphaMax, b.y * G1);
-                const bool act0 = (jb < lim0) && (pw.x <= 0.f) && (al0 >= kAlphaMin);
-                const bool act1 = (jb < lim1) && (pw.y <= 0.f) && (al1 >= kAlphaMin);
+                const float al2 = fminf(kAlphaMax, b.y * G2), al3 = fminf(kAlphaMax, b.y * G3);
+                const bool act0 = (jb < lim0) && (pwA.x <= 0.f) && (al0 >= kAlphaMin);
+                const bool act1 = (jb < lim1) && (pwA.y <= 0.f) && (al1 >= kAlphaMin);
+                const bool act2 = (jb < lim2) && (pwB.x <= 0.f) && (al2 >= kAlphaMin);
+                const bool act3 = (jb < lim3) && (pwB.y <= 0.f) && (al3 >= kAlphaMin);
                 if constexpr (STATS) {
-                    const int lanes = __popcll(__ballot(act0 || act1));
-                    ws.v[kStBwdTrips] += 1;
-                    ws.v[kStBwdEmpty] += lanes == 0;
-                    ws.v[kStBwdActivePix] += __popcll(__ballot(act0)) + __popcll(__ballot(act1));
-                    const int bin = lanes == 0 ? 0 : lanes <= 4 ? 1 : lanes <= 8 ? 2 : lanes <= 16 ? 3 : lanes <= 32 ? 4 : 5;
-                    ws.v[kStBwdHist + bin] += 1;
+                    // counted in HALF trips: one per 128-pixel half of the tile (lanes 32h .. 32h + 31) that holds a real
+                    // entry in this iteration, binned by the active lanes of that half -- the unit of the two-wave kernel
+                    // this one replaces, so bench.py's active pixels / (128 x trips) keeps its meaning
+                    const uint64_t lanes = __ballot(act0 || act1 || act2 || act3);
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        if (ti < n_half[h]) {
+                            const int nl = __popc((uint32_t)(lanes >> (32 * h)));
+                            ws.v[kStBwdTrips] += 1;
+                            ws.v[kStBwdEmpty] += nl == 0;
+                            const int bin = nl == 0 ? 0 : nl <= 4 ? 1 : nl <= 8 ? 2 : nl <= 16 ? 3 : nl <= 32 ? 4 : 5;
+                            ws.v[kStBwdHist + bin] += 1;
+                        }
+                    }
+                    ws.v[kStBwdActivePix] += __popcll(__ballot(act0)) + __popcll(__ballot(act1)) + __popcll(__ballot(act2)) +
+                                             __popcll(__ballot(act3));
                 }
-                f2 sw, dop, dch;
-                step_bwd_pair<DEPTH>(ps, act0, act1, f2{G0, G1}, f2{al0, al1}, b.y, b.z, b.w, cb, invd, sw, dop, dch);
-                // in-lane sums over the pixel pair (dx is shared):  S1 = sum w dx, S2 = sum w dy, S3 = sum w dx^2,
-                // S4 = sum w dx dy, S5 = sum w dy^2 ; the conic factors are applied once per entry at write-out
-                const f2 m = sw * dy;
-                const f2 m2 = m * dy;
-                const f2 c0 = dch * ps.dL0, c1 = dch * ps.dL1, c2 = dch * ps.dL2;
+                f2 swA, dopA, dchA, swB, dopB, dchB;
+                step_bwd_pair<DEPTH>(psA, act0, act1, f2{G0, G1}, f2{al0, al1}, b.y, b.z, b.w, cb, invd, swA, dopA, dchA);
+                step_bwd_pair<DEPTH>(psB, act2, act3, f2{G2, G3}, f2{al2, al3}, b.y, b.z, b.w, cb, invd, swB, dopB, dchB);
+                // in-lane sums over the four pixels (dx is shared), the two pairs added first, element by element, then the
+                // two elements:  S1 = sum w dx, S2 = sum w dy, S3 = sum w dx^2, S4 = sum w dx dy, S5 = sum w dy^2 ; the conic
+                // factors are applied once per entry at write-out
+                const f2 sw = swA + swB;
+                const f2 mA = swA * dyA, mB = swB * dyB;
+                const f2 m = mA + mB;
+                const f2 m2 = mA * dyA + mB * dyB;
+                const f2 c0 = dchA * psA.dL0 + dchB * psB.dL0;
+                const f2 c1 = dchA * psA.dL1 + dchB * psB.dL1;
+                const f2 c2 = dchA * psA.dL2 + dchB * psB.dL2;
                 float g[9];
                 g[0] = (sw.x + sw.y) * dx;
                 g[1] = m.x + m.y;
                 g[2] = g[0] * dx;
                 g[3] = g[1] * dx;
                 g[4] = m2.x + m2.y;
-                g[5] = dop.x + dop.y;
+                g[5] = (dopA.x + dopA.y) + (dopB.x + dopB.y);   // (pair by pair: the opacity gradient keeps the bits it had)
                 g[6] = c0.x + c0.y;
                 g[7] = c1.x + c1.y;
                 g[8] = c2.x + c2.y;
                 float g9 = 0.f;
                 if constexpr (DEPTH) {
-                    const f2 cd = dch * ps.dLd;
+                    const f2 cd = dchA * psA.dLd + dchB * psB.dLd;
                     g9 = cd.x + cd.y;
                 }
-                float t0, t1;
-                group_reduce<DEPTH>(g, g9, xor16_addr, t0, t1);
-                // 2 x 9 (10) lanes, one plain LDS store: each group into its own plane of its own entry's record
-                if (red_off >= 0) *reinterpret_cast<float*>(ent + jb + red_off) = red_t0 ? t0 : t1;
+                float t0, t1, t2;
+                row_reduce<DEPTH>(g, g9, t0, t1, t2);
+                // 4 x 9 (10) lanes, one plain LDS store: each group into its own plane of its own entry's record
+                if (red_off >= 0) *reinterpret_cast<float*>(ent + jb + red_off) = red_j == 0 ? t0 : red_j == 1 ? t1 : t2;
                 jb = jn;
             }
         }
@@ -1265,10 +1301,9 @@ render_bwd_kernel(RenderBwd p) {
         if (taken) {
             // the planes the entry's takers wrote (bit 2g + w of its activity byte), added in plane order
             float v[10] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const uint32_t ab = s_actb[threadIdx.x];
 #pragma unroll
             for (int pl = 0; pl < 4; ++pl) {
-                const bool on = (ab >> pl) & 1u;
+                const bool on = (act >> pl) & 1u;
 #pragma unroll
                 for (int q = 0; q < NV; ++q) {
                     const float x = my_ent[kAccF + NV * pl + q];
@@ -1294,13 +1329,17 @@ render_bwd_kernel(RenderBwd p) {
             float4* o = p.pair_grads + kPairF4 * slot;
             o[0] = make_float4(gmx, gmy, -0.5f * v[2], -v[3]);
             o[1] = make_float4(-0.5f * v[4], v[5], v[6], v[7]);
-            o[2] = make_float4(v[8], v[9], 0.f, 0.f);
-            if constexpr (kPairF4 == 4) o[3] = make_float4(0.f, 0.f, 0.f, 0.f);  // the record fills its 64-byte sector
+            // (the zeros are made HERE: as plain constants the compiler keeps a register quadruple of them alive across the
+            // replay loop and spills it)
+            float zero = 0.f;
+            asm volatile("" : "+v"(zero));
+            o[2] = make_float4(v[8], v[9], zero, zero);
+            if constexpr (kPairF4 == 4) o[3] = make_float4(zero, zero, zero, zero);  // the record fills its 64-byte sector
         }
     }
     if constexpr (STATS) {
         ws.flush(p.stats);
-        if (p.timeline && threadIdx.x == 0) {
+        if (p.timeline && lane == 0) {
             // one row per TILE SLOT of the launch (bidx: a queue worker serves several slots, or none)
             p.timeline[3 * bidx + 0] = t_start;
             p.timeline[3 * bidx + 1] = wall_clock64();
@@ -1431,15 +1470,19 @@ int launch_render_bwd(const hs_bwd_args& a, const hs_layout& L, hipStream_t s, u
     // (the CRF gradient's first stage as extra workgroups behind the tiles': see the kernel's head)
     if (crf_in_tail && !stats && crf_grad_args(a, L, p.crf_tail, 2)) grid += p.crf_tail.bx * p.crf_tail.planes;
     if (stats) {
-        if (a.dL_dout_invdepth) render_bwd_kernel<true, true><<<grid, kBatch, 0, s>>>(p);
-        else render_bwd_kernel<false, true><<<grid, kBatch, 0, s>>>(p);
-    } else if (a.dL_dout_invdepth) render_bwd_kernel<true, false><<<grid, kBatch, 0, s>>>(p);
-    else render_bwd_kernel<false, false><<<grid, kBatch, 0, s>>>(p);
+        if (a.dL_dout_invdepth) render_bwd_kernel<true, true><<<grid, kBwdWave, 0, s>>>(p);
+        else render_bwd_kernel<false, true><<<grid, kBwdWave, 0, s>>>(p);
+    } else if (a.dL_dout_invdepth) render_bwd_kernel<true, false><<<grid, kBwdWave, 0, s>>>(p);
+    else render_bwd_kernel<false, false><<<grid, kBwdWave, 0, s>>>(p);
     HS_LAUNCH_CHECK();
     return HS_OK;
 }
 
 int render_stats_count() { return kStCount; }
+
+// most CRF knots the tail workgroups of the render backward have LDS for (K - 1 64-bit words in the staging area of the
+// instantiation with the smaller records)
+int render_bwd_tail_max_knots() { return bwd_stage_floats(kAccF + 4 * 9) / 2 + 1; }
 
 // scratch of the CRF-gradient stage: one row of K + 1 floats per (pixel block, pose, channel)
 int64_t crf_partial_floats(int K, int64_t HW, int n_poses) {

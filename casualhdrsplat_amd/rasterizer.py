@@ -850,7 +850,9 @@ def render_stats(out_tensor: torch.Tensor, grad_color: torch.Tensor, grad_hdr: O
     """Profiling helper (bench.py's lane-utilisation / VALU-roofline leg): replays the render forward and backward of
     the call that produced `out_tensor` with the counting instantiation of the kernels (hs_render_stats) and returns
     the counters by name: (wave, entry) trips of the two compositing loops, how many found no active lane, the sum
-    of active pixels (<= 128 per trip), entries removed by the half-tile test, staged entries and batches.  (Of a
+    of active pixels (<= 128 per trip), entries removed by the half-tile test, staged entries and batches.  The backward
+    runs one wave per tile and counts HALF trips -- one per 128-pixel half of the tile that holds a real entry in an
+    iteration of its loop -- so that the figures keep the meaning they had with two waves per tile.  (Of a
     parameterization="raw" call it replays the render kernels on the activated tensors of that call: nothing is converted.)"""
     fn = out_tensor.grad_fn
     st: _State = fn.st

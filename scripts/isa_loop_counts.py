@@ -179,7 +179,7 @@ def _vregs(tok):
 
 
 def check_dpp_hazards(fns):
-    """The hand-placed wait states of render.hip's inline-asm DPP blocks (reduce_in_rows / reduce_in_quads), checked in
+    """The hand-placed wait states of render.hip's inline-asm DPP blocks (row_reduce), checked in
     the ISA the compiler actually emitted around them: gfx9 needs TWO wait states between a VALU write of a VGPR and a
     DPP read of it as the permuted source (src0), and the hazard recogniser does not look inside inline asm.  Every DPP
     instruction of every function is checked against the instructions laid out before it (one wait state each, `s_nop k`
