@@ -19,7 +19,7 @@ per-Gaussian feature channels with a finished forward's blending weights (featur
 regulariser on the blending weights of a ray (distortion.distortion_loss), and the depth-normal consistency term with the
 per-Gaussian normals it composites (normals.normal_consistency_loss, normals.gaussian_normals), and the fusion of rendered
 depth maps into a truncated signed distance volume with the triangle mesh extracted from it (tsdf.TSDFVolume,
-scene_io.save_mesh_ply).  Compute lives in
+scene_io.save_mesh_ply), and that mesh's clean-up by connected components (mesh.clean_mesh, mesh.mesh_components).  Compute lives in
 casualhdrsplat_amd/libhdrsplat.so (hand-written HIP, gfx950) reached through the C ABI of
 include/hdrsplat.h; importing the package does not load the library, calling it does, and a
 missing library is a hard error (no CPU fallback).
@@ -32,6 +32,7 @@ from .importance import ContributionStats, accumulate_abs_gradients, accumulate_
 from .knn import knn_mean_dist2
 from .losses import photometric_loss, ssim
 from .mcmc import GrowResult, RelocateResult, grow, inject_noise, regularize, relocate
+from .mesh import clean_mesh, mesh_components
 from .normals import gaussian_normals, normal_consistency_loss
 from .optim import GaussianAdam, cloud_param_groups
 from .rasterizer import (BinningOverflow, DensifyStats, GaussianRasterizationSettings, GaussianRasterizer,
@@ -51,5 +52,5 @@ __all__ = ["GaussianRasterizationSettings", "GaussianRasterizer", "DensifyStats"
            "kmeans", "kmeans_assign", "kmeans_update", "quantize_sh", "dequantize_sh", "VQResult",
            "undistorted_camera", "undistort_map", "undistort_frames", "UndistortMap",
            "composite_features", "distortion_loss", "normal_consistency_loss", "gaussian_normals",
-           "TSDFVolume"]
+           "TSDFVolume", "clean_mesh", "mesh_components"]
 __version__ = "0.1.0"

@@ -282,6 +282,14 @@ class hs_tsdf_args(C.Structure):
                 ("vertices", _fp), ("faces", _fp), ("colors", _fp)]
 
 
+class hs_mesh_args(C.Structure):
+    _fields_ = [("n_vertices", C.c_int64), ("n_faces", C.c_int64), ("min_faces", C.c_int64), ("keep_largest", C.c_int64),
+                ("remove_degenerate", C.c_int32), ("reserved", C.c_int32),
+                ("vertices", _fp), ("faces", _fp), ("colors", _fp), ("workspace", _fp), ("label", _fp), ("size", _fp),
+                ("totals", _fp), ("n_vertices_out", C.c_int64), ("n_faces_out", C.c_int64),
+                ("vertices_out", _fp), ("faces_out", _fp), ("colors_out", _fp), ("vertex_index", _fp), ("face_index", _fp)]
+
+
 def _call(args):
     """int f(const args*, void* hip_stream): the shape of most entry points"""
     return C.c_int, [C.POINTER(args), C.c_void_p]
@@ -360,6 +368,10 @@ SIGNATURES = {
     "hs_tsdf_mesh_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "hs_tsdf_mesh_plan": _call(hs_tsdf_args),
     "hs_tsdf_mesh_emit": _call(hs_tsdf_args),
+    "hs_mesh_workspace_bytes": (_i64, [_i64, _i64]),
+    "hs_mesh_components": _call(hs_mesh_args),
+    "hs_mesh_clean_plan": _call(hs_mesh_args),
+    "hs_mesh_clean_emit": _call(hs_mesh_args),
 }
 EXPORTS = tuple(SIGNATURES)
 # detected by name, and a library without them still loads: it serves every call that does not need them.  hs_max_frames: a

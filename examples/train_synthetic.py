@@ -18,6 +18,7 @@ camera motion") -- through the HIP kernels: every step is frames x (N-pose forwa
     python examples/train_synthetic.py --steps 300 --mcmc --distortion 1  # ... with the depth-distortion regulariser on the blending weights
     python examples/train_synthetic.py --steps 300 --mcmc --normal 0.05   # ... with the depth-normal consistency term on the composited normals
     python examples/train_synthetic.py --steps 300 --mcmc --distortion 0.1 --normal 0.05 --mesh out.ply   # ... and the surface: TSDF fusion + mesh
+    python examples/train_synthetic.py --steps 300 --mcmc --distortion 0.1 --normal 0.05 --mesh out.ply --mesh-keep-largest 1   # ... cleaned: one component
     python examples/train_synthetic.py --steps 300 --topk                 # ... grown by score to a budget, pruned by contribution
     python examples/train_synthetic.py --steps 200 --absgrad              # ... the published densify / prune on the AbsGS statistic
     python examples/train_synthetic.py --steps 300 --topk --absgrad       # ... the budgeted policy, scored by the AbsGS statistic
@@ -83,7 +84,8 @@ def mean_by_rows(x: torch.Tensor) -> torch.Tensor:
 def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, log_every=25, device="cuda", quiet=False,
         graph=False, capacity=None, lambda_dssim=0.0, fused_adam=False, raw=False, batch_frames=False,
         mcmc=False, cap_max=None, refine_every=25, opacity_reg=0.01, scale_reg=0.01, filter_3d=False, topk=False, absgrad=False,
-        bilagrid=False, distort=None, vq=0, distortion=None, normal=None, mesh=None):
+        bilagrid=False, distort=None, vq=0, distortion=None, normal=None, mesh=None, mesh_min_faces=None,
+        mesh_keep_largest=None):
     """Returns a dict of the run's first / last loss, PSNR and parameter errors (also what the GPU test checks).
     lambda_dssim > 0: each frame's loss is the published (1 - lambda) L1 + lambda (1 - SSIM), from the fused kernels of
     losses.photometric_loss (its scalar comes from the library's own fixed-order reduction); 0 keeps the plain L1.
@@ -151,7 +153,18 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
     bounds as the frames see it (the 1 % .. 99 % range of the back-projected depth samples plus 5 %, 160 samples along the longest
     side; the means of an MCMC cloud bound nothing: its transparent Gaussians wander far off), colour from the LDR images, in one
     integrate call, and the mesh extract_mesh returns is written to PATH (scene_io.save_mesh_ply).  The result gains `mesh`:
-    V, T, the volume's dims and voxel size.  Eager only (not with graph=True: the captured rasterizers return no depth)."""
+    V, T, the volume's dims and voxel size.  Eager only (not with graph=True: the captured rasterizers return no depth).
+    mesh_min_faces = N, mesh_keep_largest = N (only with mesh): between extract_mesh and save_mesh_ply the mesh goes through
+    mesh.clean_mesh(min_faces=N, keep_largest=N) -- the floaters' blobs next to the surface go, with the degenerate faces and the
+    vertices nothing references any more; `mesh` gains V_clean, T_clean and components (of the extracted mesh, by
+    mesh.mesh_components) and components_clean."""
+    if (mesh_min_faces is not None or mesh_keep_largest is not None) and mesh is None:
+        raise ValueError("mesh_min_faces=N (--mesh-min-faces) and mesh_keep_largest=N (--mesh-keep-largest) clean the mesh of "
+                         "mesh=PATH (--mesh): give that too")
+    if mesh_min_faces is not None and mesh_min_faces < 0:
+        raise ValueError("mesh_min_faces=N (--mesh-min-faces) must be >= 0")
+    if mesh_keep_largest is not None and mesh_keep_largest < 1:
+        raise ValueError("mesh_keep_largest=N (--mesh-keep-largest) must be >= 1")
     if mesh is not None and graph:
         raise ValueError("mesh=PATH (--mesh) is not supported together with graph=True (--graph): the surface is fused from the "
                          "rasterizer's return_alpha / return_invdepth outputs, which the captured step's rasterizers do not deliver")
@@ -579,9 +592,19 @@ def run(P=20000, W=320, H=208, frames=4, virtual=5, steps=200, seed=0, deg=1, lo
             volume = TSDFVolume.from_bounds(lo.tolist(), hi.tolist(), voxel, color=True, device=dev)
             volume.integrate(invdepths, views, fx, fy, alpha=alphas, color=torch.stack(images))
             vertices, faces, colors = volume.extract_mesh()
+            cleaned = None
+            if mesh_min_faces is not None or mesh_keep_largest is not None:
+                from casualhdrsplat_amd.mesh import clean_mesh, mesh_components
+                raw = (int(vertices.shape[0]), int(faces.shape[0]), int(mesh_components(faces, vertices.shape[0])[0].unique().numel()))
+                vertices, faces, colors = clean_mesh(vertices, faces, colors, min_faces=mesh_min_faces or 0,
+                                                     keep_largest=mesh_keep_largest)
+                cleaned = dict(V_clean=int(vertices.shape[0]), T_clean=int(faces.shape[0]), components=raw[2],
+                               components_clean=int(mesh_components(faces, vertices.shape[0])[0].unique().numel()))
             scene_io.save_mesh_ply(mesh, vertices, faces, colors)
         out["mesh"] = dict(V=int(vertices.shape[0]), T=int(faces.shape[0]), dims=volume.dims, voxel_size=volume.voxel_size,
                            observed=int((volume.weight >= 1).sum()), path=mesh)
+        if cleaned is not None:
+            out["mesh"].update(cleaned, V=raw[0], T=raw[1])
     if bilagrid:
         out["grids"] = grids.grids.detach()
     if whole:
@@ -650,15 +673,24 @@ def main(argv=None):
                     help="after training, render every captured frame sharp (one pose, mid exposure) with alpha and inverse depth, "
                          "fuse them into a TSDF volume over the bounds of the cloud as those views see it (tsdf.TSDFVolume) and write the extracted triangle "
                          "mesh to PATH as PLY; prints V, T and the volume's size.  Eager only (not with --graph)")
+    ap.add_argument("--mesh-min-faces", type=int, default=None, metavar="N",
+                    help="--mesh: drop the connected components of the mesh with fewer than N faces (mesh.clean_mesh) before it "
+                         "is written; prints the cleaned V and T and the number of components")
+    ap.add_argument("--mesh-keep-largest", type=int, default=None, metavar="N",
+                    help="--mesh: keep the N largest connected components of the mesh (mesh.clean_mesh) before it is written; with "
+                         "--mesh-min-faces a component must pass both")
     ap.add_argument("--cap-max", type=int, default=None, help="--mcmc: the budget of Gaussians the cloud grows to (default: P)")
     ap.add_argument("--refine-every", type=int, default=25, help="--mcmc: steps between two relocate + grow")
     ap.add_argument("--opacity-reg", type=float, default=0.01, help="--mcmc: weight of mean|opacity| (0.01 upstream)")
     ap.add_argument("--scale-reg", type=float, default=0.01, help="--mcmc: weight of mean|scale| (0.01 upstream)")
     a = ap.parse_args(argv)
+    if (a.mesh_min_faces is not None or a.mesh_keep_largest is not None) and not a.mesh:
+        ap.error("--mesh-min-faces and --mesh-keep-largest clean the mesh of --mesh PATH: give that too")
     r = run(a.P, a.W, a.H, a.frames, a.virtual, a.steps, a.seed, a.deg, graph=a.graph, lambda_dssim=a.lambda_dssim,
             fused_adam=a.fused_adam, raw=a.raw, batch_frames=a.batch_frames, mcmc=a.mcmc, cap_max=a.cap_max,
             refine_every=a.refine_every, opacity_reg=a.opacity_reg, scale_reg=a.scale_reg, filter_3d=a.filter_3d, topk=a.topk,
-            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq, distortion=a.distortion, normal=a.normal, mesh=a.mesh)
+            absgrad=a.absgrad, bilagrid=a.bilagrid, vq=a.vq, distortion=a.distortion, normal=a.normal, mesh=a.mesh,
+            mesh_min_faces=a.mesh_min_faces, mesh_keep_largest=a.mesh_keep_largest)
     f, l = r["first"], r["last"]
     print(f"loss {f['loss']:.5f} -> {l['loss']:.5f}; PSNR {f['psnr']:.2f} -> {l['psnr']:.2f} dB; exposure error "
           f"{f['exposure_log_err']:.4f} -> {l['exposure_log_err']:.4f}; knot error {f['knot_pos_err']:.5f} -> {l['knot_pos_err']:.5f}")
@@ -670,6 +702,8 @@ def main(argv=None):
         m = r["mesh"]
         print(f"mesh {m['path']}: V {m['V']}, T {m['T']}; volume {m['dims'][0]} x {m['dims'][1]} x {m['dims'][2]} samples of "
               f"{m['voxel_size']:.5f} ({m['observed']} observed)")
+        if "T_clean" in m:
+            print(f"mesh cleaned: V {m['V_clean']}, T {m['T_clean']}; components {m['components']} -> {m['components_clean']}")
     if a.vq:
         v = r["vq"]
         print(f"vq K {v['K']} ({'weighted by contribution' if v['weighted'] else 'unweighted'}), P {v['P']}: PSNR full vs quantised "

@@ -1551,6 +1551,75 @@ HS_API int64_t hs_tsdf_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz);
 HS_API int hs_tsdf_mesh_plan(const hs_tsdf_args* args, void* hip_stream);
 HS_API int hs_tsdf_mesh_emit(const hs_tsdf_args* args, void* hip_stream);
 
+/* (detected by name; HS_VERSION unchanged) Mesh clean-up by connected components (mesh.hip): what ends every published
+ * surface pipeline -- cluster the triangles, keep the large clusters, drop the vertices nothing references.  The mesh
+ * hs_tsdf_mesh_emit writes is raw: every floater of the cloud is a closed blob of its own next to the surface.  Integers and
+ * copies only: every result is exact, and the same bits on every run.
+ *
+ * The mesh.  vertices [V, 3] fp32, faces [T, 3] int32, colors [V, 3] fp32 or NULL; V = n_vertices, T = n_faces.
+ *   A face is VALID when its three indices are in [0, V).  An invalid face belongs to nothing, is never kept, and is counted.
+ *   Two valid faces are CONNECTED when they share a vertex INDEX (equal positions connect nothing: nothing is welded); a
+ *   COMPONENT is a class of the transitive closure, its LABEL the smallest vertex index its faces reference, its SIZE the
+ *   number of valid faces in it, degenerate ones included (the slivers around a sample of exactly 0 are what stitches the
+ *   marching-tetrahedra mesh together).
+ *   A face is DEGENERATE when two of its indices are equal or two of its corners compare equal in all three coordinates with
+ *   fp32 == (-0 = +0, a NaN equals nothing).  Collinear corners that are distinct are not looked for.
+ *   SELECTION.  The components ordered by (size descending, label ascending): keep_largest = n > 0 keeps the first
+ *   min(n, components), min_faces = m keeps those of size >= m, both given: a component must pass both.  0 = no limit.
+ *   OUTPUT.  The kept faces = the faces of kept components, minus the degenerate ones when remove_degenerate = 1, in input
+ *   order; the kept vertices = those a kept face references, in input order; face indices remapped, colours gathered with the
+ *   vertices, floats copied bit for bit.
+ *
+ * hs_mesh_components: label [T] and size [T] int32 of every face's component (-1 and 0 for an invalid face).  Five launches
+ *   (init, hook, flatten, sizes, write), no host read.  T = 0: no launch.
+ * hs_mesh_clean_plan: the components as above; with keep_largest > 0 an exact select of the n-th largest (size, ~label) over
+ *   the components in sixteen launches; then flags, two exclusive scans and totals = {V', T', components of the input, invalid
+ *   faces of the input} as four int64 IN DEVICE MEMORY.  The number of launches depends on the arguments only; nothing is read
+ *   on the host.  The workspace may hold anything before.  vertices may be NULL when remove_degenerate = 0.
+ * hs_mesh_clean_emit: n_vertices_out = V' and n_faces_out = T' as read from totals by the caller (the one host read of the
+ *   feature); writes vertices_out [V', 3], faces_out [T', 3] and, when given, colors_out [V', 3] (exactly when colors is),
+ *   vertex_index [V'] and face_index [T'] int32 (the input index of every output element) -- every element.  Between plan and
+ *   emit the mesh and the workspace must not change.  V' = T' = 0: no launch.
+ * The union-find is lock-free: no wave ever waits for another (mesh.hip argues it); integer atomics only.
+ * Traffic of the plan, in bytes: 12 T (faces) x 4 passes + 36 T gathered corners when remove_degenerate + about 40 V + 12 T of
+ *   workspace; + 8 V per select pass.  Emit: 24 T + 4 T gathered + 28 V (+ 24 V' colours, + 4 V' + 4 T' indices).
+ * Limits (HS_EINVAL, reported before any HIP call): args non-null; 0 <= n_vertices, n_faces < 2^31; faces non-null when
+ * n_faces > 0; workspace non-null, 16-byte aligned; every other pointer given 4-byte aligned (totals 8).  components: label,
+ * size non-null when n_faces > 0.  plan: min_faces, keep_largest >= 0; remove_degenerate 0 or 1, and then vertices non-null
+ * when both counts are not 0; totals non-null.  emit: 0 <= n_vertices_out <= n_vertices, 0 <= n_faces_out <= n_faces;
+ * vertices, vertices_out non-null when n_vertices_out > 0, faces_out when n_faces_out > 0; colors_out given exactly when colors
+ * is.  The caller owns every byte, nothing is allocated, cleared or copied, the work is enqueued on the caller's stream and
+ * nothing synchronises. */
+typedef struct hs_mesh_args {
+    int64_t n_vertices, n_faces;  /* V, T of the input */
+    int64_t min_faces;            /* plan: keep components of at least this many faces; 0: all */
+    int64_t keep_largest;         /* plan: keep the first n components by (size descending, label ascending); 0: all */
+    int32_t remove_degenerate;    /* plan: 1 = degenerate faces are not kept */
+    int32_t reserved;
+    const float* vertices;        /* [V, 3]: plan (the degenerate test), emit */
+    const int32_t* faces;         /* [T, 3] */
+    const float* colors;          /* [V, 3] or NULL: emit */
+    void* workspace;              /* hs_mesh_workspace_bytes(V, T) bytes: written by components and plan, read by emit */
+    int32_t* label;               /* components: [T] written */
+    int32_t* size;                /* components: [T] written */
+    int64_t* totals;              /* plan: {V', T', components, invalid faces} written, device memory */
+    int64_t n_vertices_out, n_faces_out;   /* emit: V' and T' of the plan */
+    float* vertices_out;          /* emit: [V', 3] written */
+    int32_t* faces_out;           /* emit: [T', 3] written */
+    float* colors_out;            /* emit: [V', 3] written; given exactly when colors is */
+    int32_t* vertex_index;        /* emit: [V'] written, or NULL */
+    int32_t* face_index;          /* emit: [T'] written, or NULL */
+} hs_mesh_args;
+
+/* 12 bytes per vertex (parent / label, size, flag / new index) and 4 per face (flag / new index), 8 per 256 vertices and 8 per
+ * 256 faces (the scans' sums), each of the six parts rounded up to 16, + 8192 (the select's histograms) + 64 (its state):
+ *   3 r(4 V) + r(4 T) + r(8 ceil(V / 256)) + r(8 ceil(T / 256)) + 8256,   r(x) = 16 ceil(x / 16).
+ * -1 (HS_EINVAL) outside the limits above.  No HIP call. */
+HS_API int64_t hs_mesh_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+HS_API int hs_mesh_components(const hs_mesh_args* args, void* hip_stream);
+HS_API int hs_mesh_clean_plan(const hs_mesh_args* args, void* hip_stream);
+HS_API int hs_mesh_clean_emit(const hs_mesh_args* args, void* hip_stream);
+
 /* Bench/test only: stable LSD radix sort of (u64 key, u32 value) pairs on bits [0, nbits), n < 2^30, using the
  * same pass kernel as HS_STAGE_BIN.  tmp must hold hs_sort_tmp_bytes(n).  Result in keys_out/vals_out.  The u32 at
  * byte 4 of tmp reads 2 afterwards if a pass gave up waiting (results invalid), else 0.  (The tests provoke exactly
