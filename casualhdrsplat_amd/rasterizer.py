@@ -830,14 +830,19 @@ def replay_forward(out_tensor: torch.Tensor, stages: int = L.HS_STAGE_RENDER) ->
 
 
 def replay_backward(out_tensor: torch.Tensor, grad_color: torch.Tensor, stages: int = L.HS_BWD_ALL,
-                    grad_hdr: Optional[torch.Tensor] = None) -> dict:
+                    grad_hdr: Optional[torch.Tensor] = None, grad_alpha: Optional[torch.Tensor] = None,
+                    grad_invdepth: Optional[torch.Tensor] = None) -> dict:
     """Profiling helper (bench.py's per-kernel roofline leg): re-enqueue the selected half of the
     backward of the forward call that produced `out_tensor`, outside autograd.  Of a parameterization="raw" call too the
-    gradients returned are those with respect to the ACTIVATED opacities, scales and rotations: what the kernels write."""
+    gradients returned are those with respect to the ACTIVATED opacities, scales and rotations: what the kernels write.
+    `grad_alpha` / `grad_invdepth` [H,W]: the upstream gradients of the accumulated-opacity / inverse-depth outputs, as
+    autograd would hand them to the backward (a gradient on the inverse depth needs a forward with return_invdepth)."""
     fn = out_tensor.grad_fn
     dev = out_tensor.device
     return _launch_backward(fn.st, fn.saved_tensors[:9], _f32c(grad_color, dev),
-                            None if grad_hdr is None else _f32c(grad_hdr, dev), stages)
+                            None if grad_hdr is None else _f32c(grad_hdr, dev), stages,
+                            galpha=None if grad_alpha is None else _f32c(grad_alpha, dev),
+                            ginvd=None if grad_invdepth is None else _f32c(grad_invdepth, dev))
 
 
 RENDER_STAT_NAMES = ("bwd_trips", "bwd_empty_trips", "bwd_active_pixels", "bwd_culled", "bwd_hist_0", "bwd_hist_1_4",

@@ -232,8 +232,10 @@ def pixel_reach(cam: Camera, fwd: dict, pix_mask, whole_list: bool = False, guar
 
 def backward(cam: Camera, fwd: dict, dL_dcolor_img, means3D, shs=None, colors_precomp=None,
              scales=None, rotations=None, cov3D_precomp=None, dL_dinvdepth_img=None, bounds: bool = False,
-             conditioned: bool = False) -> dict:
-    """Runs a10..a12 given forward()'s intermediates and dL/d(out_color) [3,H,W] (+ optional dL/d(invdepth) [H,W]).
+             conditioned: bool = False, dL_dalpha_img=None) -> dict:
+    """Runs a10..a12 given forward()'s intermediates and dL/d(out_color) [3,H,W] (+ optional dL/d(invdepth) [H,W] and
+    dL/d(accumulated opacity) [H,W], A = 1 - final_T: dA/dalpha_i = T_final / (1 - alpha_i), the background term with its
+    dot product reduced by the pixel's dL/dA; its magnitude enters abs_* / cond_* next to the background term's).
 
     bounds=True adds, next to every gradient tensor `dL_dX`, `abs_dL_dX` of the same shape = sum |terms| of that
     element, and `n_terms` [P]: the render backward returns, for each of its ten per-Gaussian sums, the sum over the
@@ -268,6 +270,10 @@ def backward(cam: Camera, fwd: dict, dL_dcolor_img, means3D, shs=None, colors_pr
                _p(fwd["depths"]) if gd is not None else None, _p(gd), _p(o["dL_dinvdepth"]))
     if conditioned:
         o["cond_terms"] = np.zeros((P, 10), np.float32)
+    if dL_dalpha_img is not None:
+        ga = _f32(dL_dalpha_img).reshape(cam.H, cam.W)
+        rc = L.hso_render_bwd_alpha(*rb_args, _p(o.get("cond_terms")), _p(ga))
+    elif conditioned:
         rc = L.hso_render_bwd_cond(*rb_args, _p(o["cond_terms"]))
     else:
         rc = L.hso_render_bwd(*rb_args)

@@ -663,7 +663,8 @@ int64_t hso_pixel_reach_cond(const hso_camera* c, const uint32_t* ranges, const 
  * abs_terms (optional, may be NULL; [P, 11]) receives, next to every one of the ten per-Gaussian sums (order: mean2D x, y;
  * conic A, B, C; opacity; colour r, g, b; inverse depth), the sum over the pixels of  w * |term|:  |term| = the per-pixel
  * term evaluated with every difference inside it replaced by the sum of the absolute values of its operands
- * (|c - accum| -> |c| + |accum|, the background term's sum of |bg_ch dL_ch|, |gdx A| + |gdy B| ...), i.e. the scale against
+ * (|c - accum| -> |c| + |accum|, the background term's sum of |bg_ch dL_ch| (+ |dL/dA| of the accumulated-opacity image),
+ * |gdx A| + |gdy B| ...), i.e. the scale against
  * which an fp32 evaluation of that term, in any operation order, is accurate to a few ulp; w = 4 + the number of
  * T <- T / (1 - alpha) steps the replay has taken on that pixel before this contributor -- every step adds an ulp to T's
  * relative error, and T multiplies the whole term (the conditioning DESIGN.md's numerical contract speaks of) -- and in
@@ -675,9 +676,12 @@ static int render_bwd_impl(const hso_camera* c, const uint32_t* ranges, const ui
                    const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
                    float* abs_terms,
-                   const float* depths, const float* dL_dinvdepth_pix, float* dL_dinvdepth, float* cond_terms) {
+                   const float* depths, const float* dL_dinvdepth_pix, float* dL_dinvdepth, float* cond_terms,
+                   const float* dL_dalpha_pix) {
     /* depths, dL_dinvdepth_pix [H*W], dL_dinvdepth [P] (all or none): the inverse-depth image is a fourth blended
      * channel without a background term; dL_dinvdepth receives sum_pix alpha T dL/dD(pix) per Gaussian */
+    /* dL_dalpha_pix [H*W] (may be NULL): dL/dA of the accumulated-opacity image A = 1 - T_final.  dA/dalpha_i =
+     * T_final / (1 - alpha_i): the background term below with bg_dot reduced by the pixel's dL/dA */
     const int W = c->W, H = c->H, P = c->P;
     const int gx = (W + HSO_TILE - 1) / HSO_TILE;
     double* acc = (double*)calloc((size_t)P * 11, sizeof(double));
@@ -699,6 +703,8 @@ static int render_bwd_impl(const hso_camera* c, const uint32_t* ranges, const ui
             float dLp[3];
             for (int ch = 0; ch < 3; ++ch) dLp[ch] = dL_dpix[(size_t)ch * H * W + pix];
             float bg_dot = (c->bg[0] * dLp[0] + c->bg[1] * dLp[1]) + c->bg[2] * dLp[2];
+            const float dLa = dL_dalpha_pix ? dL_dalpha_pix[pix] : 0.f;
+            if (dL_dalpha_pix) bg_dot -= dLa;
             float accum_rec[3] = {0.f, 0.f, 0.f}, last_color[3] = {0.f, 0.f, 0.f};
             float accum_invd = 0.f, last_invd = 0.f;
             const float dLd = dL_dinvdepth_pix ? dL_dinvdepth_pix[pix] : 0.f;
@@ -759,7 +765,8 @@ static int render_bwd_impl(const hso_camera* c, const uint32_t* ranges, const ui
                 last_alpha = alpha;
                 dL_dalpha += (-T_final / (1.f - alpha)) * bg_dot;
                 mag_alpha += fabs((double)(T_final / (1.f - alpha))) *
-                             ((fabs((double)(c->bg[0] * dLp[0])) + fabs((double)(c->bg[1] * dLp[1]))) + fabs((double)(c->bg[2] * dLp[2])));
+                             (((fabs((double)(c->bg[0] * dLp[0])) + fabs((double)(c->bg[1] * dLp[1]))) + fabs((double)(c->bg[2] * dLp[2]))) +
+                              fabs((double)dLa));
                 float dL_dG = co[3] * dL_dalpha;
                 float gdx = G * dx, gdy = G * dy;
                 float dG_ddelx = -gdx * co[0] - gdy * co[1];
@@ -820,7 +827,7 @@ int hso_render_bwd(const hso_camera* c, const uint32_t* ranges, const uint32_t* 
                    float* abs_terms,
                    const float* depths, const float* dL_dinvdepth_pix, float* dL_dinvdepth) {
     return render_bwd_impl(c, ranges, point_list, xy, conic_opacity, rgb, final_T, n_contrib, dL_dpix, dL_dmean2D, dL_dconic,
-                           dL_dopacity, dL_dcolor, abs_terms, depths, dL_dinvdepth_pix, dL_dinvdepth, NULL);
+                           dL_dopacity, dL_dcolor, abs_terms, depths, dL_dinvdepth_pix, dL_dinvdepth, NULL, NULL);
 }
 
 /* hso_render_bwd that also returns cond_terms [P, 10]: the ten magnitude sums of abs_terms (same order, same |term|) with
@@ -839,7 +846,23 @@ int hso_render_bwd_cond(const hso_camera* c, const uint32_t* ranges, const uint3
         !dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor)
         return -1;
     return render_bwd_impl(c, ranges, point_list, xy, conic_opacity, rgb, final_T, n_contrib, dL_dpix, dL_dmean2D, dL_dconic,
-                           dL_dopacity, dL_dcolor, abs_terms, depths, dL_dinvdepth_pix, dL_dinvdepth, cond_terms);
+                           dL_dopacity, dL_dcolor, abs_terms, depths, dL_dinvdepth_pix, dL_dinvdepth, cond_terms, NULL);
+}
+
+/* hso_render_bwd / hso_render_bwd_cond (cond_terms may be NULL here) with a gradient on the accumulated-opacity image:
+ * dL_dalpha_pix [H*W] = dL/dA, A = 1 - T_final.  Its magnitude enters abs_terms / cond_terms next to the background term's. */
+int hso_render_bwd_alpha(const hso_camera* c, const uint32_t* ranges, const uint32_t* point_list,
+                         const float* xy, const float* conic_opacity, const float* rgb,
+                         const float* final_T, const uint32_t* n_contrib, const float* dL_dpix,
+                         float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor,
+                         float* abs_terms,
+                         const float* depths, const float* dL_dinvdepth_pix, float* dL_dinvdepth, float* cond_terms,
+                         const float* dL_dalpha_pix) {
+    if (!c || !ranges || !point_list || !xy || !conic_opacity || !rgb || !final_T || !n_contrib || !dL_dpix ||
+        !dL_dmean2D || !dL_dconic || !dL_dopacity || !dL_dcolor)
+        return -1;
+    return render_bwd_impl(c, ranges, point_list, xy, conic_opacity, rgb, final_T, n_contrib, dL_dpix, dL_dmean2D, dL_dconic,
+                           dL_dopacity, dL_dcolor, abs_terms, depths, dL_dinvdepth_pix, dL_dinvdepth, cond_terms, dL_dalpha_pix);
 }
 
 /* ------------------------------------------------------------------------------------------

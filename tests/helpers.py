@@ -36,8 +36,11 @@ def settings_from_scene(sc: S.Scene, device, cameras=None, hdr=False, blur_domai
 
 
 def run_hip(sc: S.Scene, device="cuda", cameras=None, hdr=False, blur_domain="ldr", backward=True, capacity=None,
-            use_cov_precomp=None, use_colors_precomp=None, grad_hdr=None, radiance_activation="relu_shift", dL_image=None):
-    """Forward (+ backward with sc.dL_dimage, or `dL_image` [3,H,W] when given) through GaussianRasterizer on the GPU."""
+            use_cov_precomp=None, use_colors_precomp=None, grad_hdr=None, radiance_activation="relu_shift", dL_image=None,
+            invdepth_grad=None, alpha_grad=None):
+    """Forward (+ backward with sc.dL_dimage, or `dL_image` [3,H,W] when given) through GaussianRasterizer on the GPU.
+    `invdepth_grad` / `alpha_grad` [H,W]: turn on return_invdepth / return_alpha, add sum(output * gradient) to the loss and
+    return the images as res["invdepth"] / res["alpha"]."""
     from casualhdrsplat_amd import GaussianRasterizer, inspect_state
     rs, exposure, crf = settings_from_scene(sc, device, cameras, hdr, blur_domain, requires_grad=backward,
                                             radiance_activation=radiance_activation)
@@ -60,11 +63,20 @@ def run_hip(sc: S.Scene, device="cuda", cameras=None, hdr=False, blur_domain="ld
     else:
         kwargs["scales"] = mk("scales", sc.scales)
         kwargs["rotations"] = mk("rotations", sc.rotations)
-    rast = GaussianRasterizer(rs, capacity=capacity)
+    rast = GaussianRasterizer(rs, capacity=capacity, return_alpha=alpha_grad is not None,
+                              return_invdepth=invdepth_grad is not None)
     out = rast(means3D, means2D, opac, **kwargs)
     res = {"color": out[0].detach().cpu().numpy(), "radii": out[1].cpu().numpy()}
     if hdr:
         res["hdr"] = out[2].detach().cpu().numpy()
+    # (the outputs' order: colour, radii, [radiance], [accumulated opacity], [inverse depth])
+    extra = []
+    nxt = 3 if hdr else 2
+    for name, up in (("alpha", alpha_grad), ("invdepth", invdepth_grad)):
+        if up is not None:
+            res[name] = out[nxt].detach().cpu().numpy()
+            extra.append((out[nxt], torch.as_tensor(np.asarray(up, np.float32))))
+            nxt += 1
     if backward:
         st = inspect_state(out[0])
         res["state"] = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in st.items()}
@@ -72,6 +84,8 @@ def run_hip(sc: S.Scene, device="cuda", cameras=None, hdr=False, blur_domain="ld
         loss = (out[0] * dL_t.to(device)).sum()
         if grad_hdr is not None:
             loss = loss + (out[2] * grad_hdr.to(device)).sum()
+        for img, up in extra:
+            loss = loss + (img * up.to(device)).sum()
         loss.backward()
         for k, v in leaf.items():
             res["d_" + k] = v.grad.detach().cpu().numpy() if v.grad is not None else None
@@ -143,6 +157,19 @@ def sweep_case(rng, case: int) -> dict:
                 precomp=precomp, colors=colors, what=what)
 
 
+def optional_outputs_case(rng, c: dict) -> dict:
+    """What a case of the optional-outputs sweep (tests/test_optional_outputs_gpu.py) draws AFTER sweep_case(rng, case) gave
+    `c`: which of the inverse-depth and accumulated-opacity outputs carry an upstream gradient (0: inverse depth, 1: opacity,
+    2: both) and those gradients, N(0, 1) x 3 -- the same order of magnitude as the colour's.  Kept out of sweep_case so that
+    the draws of the existing sweep do not move."""
+    which = int(rng.integers(0, 3))
+    gD = (rng.standard_normal((c["H"], c["W"])) * 3.0).astype(np.float32)
+    gA = (rng.standard_normal((c["H"], c["W"])) * 3.0).astype(np.float32)
+    names = ("invdepth", "alpha", "invdepth+alpha")[which]
+    return dict(which=names, invdepth_grad=gD if which != 1 else None, alpha_grad=gA if which != 0 else None,
+                what=c["what"] + f" outputs={names}")
+
+
 def oracle_camera(O, sc: S.Scene, cam=None, radiance_activation="relu_shift"):
     cam = cam or sc.camera
     oc = O.Camera(cam.W, cam.H, cam.tanfovx, cam.tanfovy, cam.viewmatrix.numpy(), cam.projmatrix.numpy(),
@@ -153,8 +180,9 @@ def oracle_camera(O, sc: S.Scene, cam=None, radiance_activation="relu_shift"):
 
 
 def run_oracle(O, sc: S.Scene, cam=None, dL=None, backward=True, use_cov_precomp=None, use_colors_precomp=None,
-               radiance_activation="relu_shift", bounds=False):
-    """Single-pose LDR/linear render through the C oracle (a4..a12)."""
+               radiance_activation="relu_shift", bounds=False, dL_invdepth=None, dL_alpha=None):
+    """Single-pose LDR/linear render through the C oracle (a4..a12); `dL_invdepth` / `dL_alpha` [H,W]: gradients on the
+    inverse-depth and accumulated-opacity images next to the colour's."""
     ocam = oracle_camera(O, sc, cam, radiance_activation)
     kw = {}
     if use_colors_precomp is not None:
@@ -170,7 +198,8 @@ def run_oracle(O, sc: S.Scene, cam=None, dL=None, backward=True, use_cov_precomp
     b = None
     if backward:
         dL = sc.dL_dimage.numpy() if dL is None else dL
-        b = O.backward(ocam, f, dL, sc.means3D.numpy(), bounds=bounds, **kw)
+        b = O.backward(ocam, f, dL, sc.means3D.numpy(), bounds=bounds, dL_dinvdepth_img=dL_invdepth, dL_dalpha_img=dL_alpha,
+                       **kw)
     return f, b
 
 
@@ -208,12 +237,16 @@ def _pose_map(fn, items, workers):
 
 
 def run_oracle_hdr(O, sc: S.Scene, cameras=None, blur_domain="ldr", dL_ldr=None, dL_hdr=None,
-                   radiance_activation="relu_shift", workers=1, fwds=None, bounds=False):
+                   radiance_activation="relu_shift", workers=1, fwds=None, bounds=False, dL_invdepth=None, dL_alpha=None):
     """HDR image formation with the C oracle: per pose H_k (a4..a9), tone-map (a15), average over poses;
     backward chains tonemap_bwd into the rasterizer backward per pose and sums (in pose order, whatever `workers`).
-    Returns dict of outputs and gradients (numpy)."""
+    Returns dict of outputs and gradients (numpy).
+    `dL_invdepth` / `dL_alpha` [H,W]: gradients on the frame's inverse-depth / accumulated-opacity image; both images are
+    the mean over the poses (rasterizer.py), so every pose's backward takes 1 / N of them."""
     cams = cameras or [sc.camera]
     N = len(cams)
+    share = lambda g: None if g is None else (np.asarray(g, np.float32) / np.float32(N)).astype(np.float32)
+    gD, gA = share(dL_invdepth), share(dL_alpha)
     dL_ldr = sc.dL_dimage.numpy() if dL_ldr is None else dL_ldr
     dt = float(sc.exposure)
     tab = sc.crf_table.numpy()
@@ -245,7 +278,8 @@ def run_oracle_hdr(O, sc: S.Scene, cameras=None, blur_domain="ldr", dL_ldr=None,
             dH = dH + dL_hdr / N
         ocam = oracle_camera(O, sc, cams[k], radiance_activation)
         b = O.backward(ocam, fs[k], dH.astype(np.float32), sc.means3D.numpy(), shs=sc.shs.numpy(),
-                       scales=sc.scales.numpy(), rotations=sc.rotations.numpy(), bounds=bounds)
+                       scales=sc.scales.numpy(), rotations=sc.rotations.numpy(), bounds=bounds, dL_dinvdepth_img=gD,
+                       dL_dalpha_img=gA)
         return {q: b[q] for q in keys + ((["abs_" + q for q in keys] + ["n_terms"]) if bounds else [])}, dtab, dexp
 
     for b, dtab, dexp in _pose_map(pose_backward, range(N), workers):
@@ -645,13 +679,15 @@ def crf_grad_bound(sc: S.Scene, ref_imgs, dL_ldr, c=6.0):
 
 
 def run_oracle_poses(O, sc: S.Scene, cameras, dL, fwds, radiance_activation="relu_shift", bounds=False, workers=1,
-                     use_cov_precomp=None, use_colors_precomp=None, conditioned=False):
+                     use_cov_precomp=None, use_colors_precomp=None, conditioned=False, dL_invdepth=None, dL_alpha=None):
     """Backward of the non-HDR N-pose frame (the linear-radiance blur: the output is the mean of the per-pose renders) with
     the C oracle: sum over the poses, in pose order, of backward(dL / N) given each pose's forward in `fwds`; with
-    `bounds`, the abs_* magnitudes (and n_terms) are summed alongside."""
+    `bounds`, the abs_* magnitudes (and n_terms) are summed alongside.  `dL_invdepth` / `dL_alpha` [H,W]: the inverse-depth
+    and accumulated-opacity images are means over the poses too, so each pose takes 1 / N of those as well."""
     N = len(cameras)
     dLn = (np.asarray(dL, np.float32) / np.float32(N)).astype(np.float32)
-    kw = {}
+    share = lambda g: None if g is None else (np.asarray(g, np.float32) / np.float32(N)).astype(np.float32)
+    kw = dict(dL_dinvdepth_img=share(dL_invdepth), dL_dalpha_img=share(dL_alpha))
     if use_colors_precomp is not None:
         kw["colors_precomp"] = use_colors_precomp.numpy()
     else:
@@ -680,22 +716,29 @@ def run_oracle_poses(O, sc: S.Scene, cameras, dL, fwds, radiance_activation="rel
 
 
 def masked_backward_pass(O, sc: S.Scene, masks, fwds, cameras=None, hdr=True, blur_domain="ldr", workers=1, what="",
-                         radiance_activation="relu_shift", use_cov_precomp=None, use_colors_precomp=None, conditioned=False):
+                         radiance_activation="relu_shift", use_cov_precomp=None, use_colors_precomp=None, conditioned=False,
+                         invdepth_grad=None, alpha_grad=None):
     """The second backward of VERDICT r4 next #2: dL zeroed on masks["excluded"] on BOTH sides (the HIP path renders and
     differentiates the frame again with the masked dL, the oracle reuses its forwards).  Returns (got, ref, dL_masked);
     the caller holds EVERY row to its bar (no at_risk) and every element to assert_grads_bounded.  Frames: HDR (one or N
     poses, either blur domain), and linear radiance of one pose (precomputed colours / covariances allowed) or of N poses
-    (the mean of the per-pose renders: the oracle reference is sum_k backward(dL / N))."""
-    dLm = np.asarray(sc.dL_dimage.numpy(), np.float32) * (~masks["excluded"])[None].astype(np.float32)
+    (the mean of the per-pose renders: the oracle reference is sum_k backward(dL / N)).
+    `invdepth_grad` / `alpha_grad` [H,W]: gradients on the inverse-depth / accumulated-opacity outputs, zeroed on
+    masks["excluded"] on both sides like the colour's."""
+    keep = (~masks["excluded"]).astype(np.float32)
+    dLm = np.asarray(sc.dL_dimage.numpy(), np.float32) * keep[None]
+    gD = None if invdepth_grad is None else np.asarray(invdepth_grad, np.float32) * keep
+    gA = None if alpha_grad is None else np.asarray(alpha_grad, np.float32) * keep
     got = run_hip(sc, cameras=cameras, hdr=hdr, blur_domain=blur_domain, dL_image=dLm, radiance_activation=radiance_activation,
-                  use_cov_precomp=use_cov_precomp, use_colors_precomp=use_colors_precomp)
+                  use_cov_precomp=use_cov_precomp, use_colors_precomp=use_colors_precomp, invdepth_grad=gD, alpha_grad=gA)
     if hdr:
         assert use_cov_precomp is None and use_colors_precomp is None and not conditioned
         ref = run_oracle_hdr(O, sc, cameras, blur_domain, dL_ldr=dLm, workers=workers, fwds=fwds, bounds=True,
-                             radiance_activation=radiance_activation)
+                             radiance_activation=radiance_activation, dL_invdepth=gD, dL_alpha=gA)
     else:
         ref = run_oracle_poses(O, sc, cameras or [sc.camera], dLm, fwds, radiance_activation, bounds=True, workers=workers,
-                               use_cov_precomp=use_cov_precomp, use_colors_precomp=use_colors_precomp, conditioned=conditioned)
+                               use_cov_precomp=use_cov_precomp, use_colors_precomp=use_colors_precomp, conditioned=conditioned,
+                               dL_invdepth=gD, dL_alpha=gA)
     return got, ref, dLm
 
 

@@ -263,7 +263,7 @@ def _bound_scene(oracle, name):
         sc.scales *= 60.0
     elif name == "deep":               # faint layers: long contributor lists, no early termination
         sc.opacities *= 0.05
-    elif name == "antialias":
+    elif name in ("antialias", "invdepth_alpha_antialias"):
         sc.antialias = True
         sc.scale_modifier = 0.7
     elif name == "precomp":
@@ -277,7 +277,16 @@ def _bound_scene(oracle, name):
     return sc, act, cols, cov
 
 
-BOUND_SCENES = ["plain", "free_camera", "wild", "giants", "deep", "antialias", "precomp", "relu_shift", "exp", "softplus"]
+BOUND_SCENES = ["plain", "free_camera", "wild", "giants", "deep", "antialias", "precomp", "relu_shift", "exp", "softplus",
+                "invdepth", "alpha", "invdepth_alpha_antialias"]
+
+
+def _optional_output_gradients(name, H, W, keep):
+    """Upstream gradients on the inverse-depth / accumulated-opacity images of the scenes named after them (None: the output
+    is not part of the loss), masked by the guard band like the colour's."""
+    gen = torch.Generator().manual_seed(11)
+    gD, gA = ((torch.randn(H, W, generator=gen) * 3.0 * torch.from_numpy(keep.astype(np.float32))).contiguous() for _ in range(2))
+    return (gD if "invdepth" in name else None), (gA if "alpha" in name else None)
 
 
 @pytest.mark.parametrize("name", BOUND_SCENES)
@@ -291,7 +300,10 @@ def test_c_oracle_within_the_gradient_bound_of_fp64(oracle, name):
     held to the bound -- zero elements outside.  The twin's render reads the fp32 preprocess outputs (screen position,
     conic, opacity, colour -- bit-exact between the HIP path and the oracle, which every GPU test asserts) through a
     straight-through pin: the bound covers the sums of the backward, not the rounding of the projection (unpinned, a
-    "deep" scene puts one element at c = 41: dx = x - px of a pixel next to the centre, relative error ulp(x) / dx)."""
+    "deep" scene puts one element at c = 41: dx = x - px of a pixel next to the centre, relative error ulp(x) / dx).
+    Scenes `invdepth`, `alpha`, `invdepth_alpha_antialias`: the loss also takes the expected inverse depth and / or the
+    accumulated opacity A = 1 - T_final with gradients of their own (masked the same way) -- the oracle's dL_dinvdepth_img /
+    dL_dalpha_img inputs and the magnitudes they add to sum w|term|."""
     sc, act, cols, cov = _bound_scene(oracle, name)
     pre = {}
     if cols is not None:
@@ -301,7 +313,9 @@ def test_c_oracle_within_the_gradient_bound_of_fp64(oracle, name):
     keep = ~pix_risk[0]
     assert keep.mean() > 0.9, (name, float(keep.mean()))
     dLm = (sc.dL_dimage * torch.from_numpy(keep.astype(np.float32))[None]).contiguous()
-    _, b = Hh.run_oracle(oracle, sc, dL=dLm.numpy(), radiance_activation=act, bounds=True, **pre)
+    gD, gA = _optional_output_gradients(name, sc.camera.H, sc.camera.W, keep)
+    _, b = Hh.run_oracle(oracle, sc, dL=dLm.numpy(), radiance_activation=act, bounds=True,
+                         dL_invdepth=None if gD is None else gD.numpy(), dL_alpha=None if gA is None else gA.numpy(), **pre)
 
     dt = torch.float64
     leaves = {k: getattr(sc, k).to(dt).clone().requires_grad_(True) for k in ["means3D", "opacities"]}
@@ -329,15 +343,21 @@ def test_c_oracle_within_the_gradient_bound_of_fp64(oracle, name):
         pinned = x + (torch.from_numpy(np.ascontiguousarray(v)).to(dt) - x).detach()
         pre_[k] = torch.where(vis, pinned, x).reshape(pre_[k].shape)
     point_list, ranges, _ = TR.bin_tiles(view, pre_)
-    color, final_T, n_contrib = TR.render(view, pre_, point_list, ranges, sc.bg)
-    st = dict(pre=pre_, point_list=point_list, final_T=final_T, n_contrib=n_contrib)
+    color, final_T, n_contrib, invdepth = TR.render(view, pre_, point_list, ranges, sc.bg, want_invdepth=True)
+    st = dict(pre=pre_, point_list=point_list, final_T=final_T, n_contrib=n_contrib, invdepth=invdepth)
     # identical structure, and decisions that differ only inside the guard band (whose pixels carry no dL here)
     assert np.array_equal(st["point_list"].numpy(), f["point_list"].astype(np.int64)), name
     assert np.array_equal(st["pre"]["radii"].numpy(), f["radii"]), name
     Tf = st["final_T"].detach().numpy()
     differ = (st["n_contrib"].numpy() != f["n_contrib"]) | (np.abs(f["final_T"] - Tf) > 2e-3 * np.maximum(Tf, 1e-4))
     assert not (differ & keep).any(), (name, int((differ & keep).sum()))
-    (color * dLm.to(dt)).sum().backward()
+    loss = (color * dLm.to(dt)).sum()
+    if gD is not None:      # the two optional images of the rasterizer: expected inverse depth, A = 1 - T_final
+        assert Hh.rel_err(f["invdepth"][keep], st["invdepth"].detach().numpy()[keep], 1e-3)[0] < 1e-5, name
+        loss = loss + (st["invdepth"] * gD.to(dt)).sum()
+    if gA is not None:
+        loss = loss + ((1.0 - st["final_T"]) * gA.to(dt)).sum()
+    loss.backward()
     got = {"d_" + k: b[rk] for k, rk in keys}
     ref = {rk: leaves[k].grad.numpy().reshape(b[rk].shape) for k, rk in keys}
     ref.update({"abs_" + rk: b["abs_" + rk] for _, rk in keys})

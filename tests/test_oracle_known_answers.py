@@ -63,6 +63,38 @@ def test_alpha_clamped_at_099_and_skipped_below_1_255(oracle):
     assert np.all(f["color"] == 0) and np.all(f["n_contrib"] == 0) and np.all(f["final_T"] == 1)
 
 
+def test_opacity_and_inverse_depth_gradients_of_one_gaussian_over_one_pixel(oracle):
+    """One Gaussian, an upstream gradient of 1 on ONE pixel of the accumulated-opacity image A, then of the inverse-depth
+    image D, the colour's all zero.  There A = alpha and D = alpha / z with alpha = o G, G the footprint's value at that pixel:
+    dA/do = G and dD/do = G / z."""
+    W = H = 64
+    sigma, o, z, d = 3.0, 0.7, 5.0, 4
+    f, oc = iso(oracle, W, H, 32, 32, z, sigma, o, (0.3, 0.6, 0.9), bg=(0.2, 0.4, 0.1))
+    G = math.exp(-d * d / (2 * (sigma * sigma + 0.3)))
+    assert o * G >= 1 / 255 and f["n_contrib"][32, 32 + d] == 1
+    assert 1.0 - f["final_T"][32, 32 + d] == pytest.approx(o * G, rel=2e-4)
+    assert f["invdepth"][32, 32 + d] == pytest.approx(o * G / z, rel=2e-4)
+    one = np.zeros((H, W), np.float32)
+    one[32, 32 + d] = 1.0
+    fx = W / (2 * oc.tanfovx)
+    kw = dict(colors_precomp=np.array([[0.3, 0.6, 0.9]], np.float32), scales=np.full((1, 3), sigma * z / fx, np.float32),
+              rotations=np.array([[1, 0, 0, 0]], np.float32))
+    means = np.array([point_at_pixel(S.make_camera(W, H), 32, 32, z)], np.float32)
+    zero = np.zeros((3, H, W), np.float32)
+    bA = oracle.backward(oc, f, zero, means, dL_dalpha_img=one, bounds=True, **kw)
+    assert bA["dL_dopacity"][0] == pytest.approx(G, rel=2e-4)
+    assert bA["abs_dL_dopacity"][0] >= abs(bA["dL_dopacity"][0])           # the magnitude sum carries the term (w >= 4)
+    assert np.all(bA["dL_dcolors_precomp"] == 0)
+    bD = oracle.backward(oc, f, zero, means, dL_dinvdepth_img=one, **kw)
+    assert bD["dL_dopacity"][0] == pytest.approx(G / z, rel=2e-4)
+    # both at once, with weights: the two terms add
+    bB = oracle.backward(oc, f, zero, means, dL_dinvdepth_img=2.0 * one, dL_dalpha_img=-3.0 * one, **kw)
+    assert bB["dL_dopacity"][0] == pytest.approx(2.0 * G / z - 3.0 * G, rel=2e-4)
+    # without the new input nothing moves
+    b0 = oracle.backward(oc, f, zero, means, **kw)
+    assert b0["dL_dopacity"][0] == 0.0
+
+
 def two_gaussians(O, z_a, z_b):
     W = H = 32
     oc, c = cam_for(O, W, H)
