@@ -23,9 +23,10 @@
 // A binning overflow (hs_counters.overflow != 0) is seen ON THE DEVICE: the fold then writes nothing.
 //
 // This unit is compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS), so that the threshold tests below
-// see the bits the forward's saw; the expressions are the forward's and the backward's, operand for operand.  The forward's
-// decisions a replay repeats (pixel mapping, XCD strip map, staged conic, thresholds, pair_act bits, walk bound, pair slots),
-// the tile context, the segmented sum and the workspace layout are hs_replay.h's, shared with contrib.hip.
+// see the bits the forward's saw.  The forward's decisions a replay repeats (pixel mapping, XCD strip map, staged conic, alpha
+// and thresholds, pair_act bits, walk bound, pair slots), the staging of an entry, the back-to-front walk (take lists,
+// sentinel, T recursion), the combination of the planes, the tile context, the segmented sum and the workspace layout are
+// hs_replay.h's; the rest of the backward's step is render.hip's step_bwd_pair, operand for operand.
 #include "hs_replay.h"
 
 namespace hs {
@@ -39,12 +40,6 @@ constexpr int kAThreads = 128;       // threads per workgroup: two waves, one pe
 constexpr int kABatch = 128;
 
 static_assert(kABatch % 64 == 0 && kABatch <= kAThreads, "the lists are built from whole ballots, one entry is staged per thread");
-
-__device__ __forceinline__ f2 splat(float v) { f2 r = {v, v}; return r; }
-// number of set bits of a wave-uniform 64-bit mask below this lane
-__device__ __forceinline__ int mask_prefix(uint64_t m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
 
 struct Crf {
     const float* table;  // [3,K]
@@ -142,19 +137,18 @@ __device__ __forceinline__ void load_pixel_bwd(const Replay& p, PixB& s, bool in
 template <bool DEPTH>
 __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
     constexpr int KB = kABatch;
-    constexpr int kListLen = KB + 8;
-    // (record KB of the staging arrays: the sentinel, opacity 0 -- nobody composites it; it pads the shorter list of a wave)
+    // (record KB of the staging arrays: the back-to-front walk's sentinel)
     __shared__ float4 s_a[KB + 1];        // {x, y, A2, B2}
     __shared__ float4 s_b[KB + 1];        // {C2, opacity, r, g}
     __shared__ float4 s_c[KB + 1];        // {b, 1 / depth (DEPTH) or depth, radius (int bits), slot start (uint bits)}
     __shared__ float2 s_part[KB + 1][4];  // plane 2g + w: the totals of lane group g of wave w, stored by that group alone
     __shared__ uint8_t s_actb[kAThreads]; // activity byte of each staged entry (bit 2g + w)
-    __shared__ uint16_t s_list[2][2][kListLen];   // [wave][lane group]: the group's takers among the staged entries, back to front
+    __shared__ uint16_t s_list[2][2][KB + 8];     // [wave][lane group]: the group's takers among the staged entries, back to front
     __shared__ uint32_t s_max[2];
 
     if (p.counters->overflow) return;     // (ReplayFrame: the frame adds nothing)
     const TileCtx tc = tile_context(p);
-    const int wave = tc.wave, lane = tc.lane, plane = act_plane(tc.grp, tc.wave);
+    const int lane = tc.lane, plane = act_plane(tc.grp, tc.wave);
 
     PixB s0, s1;
     load_pixel_bwd(p, s0, tc.in0, tc.pose, tc.frame, tc.px, tc.py0);
@@ -170,7 +164,6 @@ __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
     __syncthreads();
     const int n_proc = walk_bound(s_max, tc);
 
-    const uint16_t* const my_list = s_list[wave][tc.grp];
     // |t_x| = |A dx + B dy| |w| W / 2 with A = -2 A2 / log2(e), B = -B2 / log2(e): the sums are kept in the staged (scaled)
     // conic's units, the positive factor is applied once per pair at write-out
     const float kx = 0.5f * (float)p.W / kLog2e, ky = 0.5f * (float)p.H / kLog2e;
@@ -182,95 +175,50 @@ __global__ void __launch_bounds__(kAThreads) absgrad_replay_kernel(Replay p) {
         __syncthreads();   // the previous batch's write-out has read its records
         uint32_t act = 0;
         if ((int)threadIdx.x < cnt) {
-            const uint32_t id = min(p.point_list[tc.range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
-            act = p.pair_act[(int64_t)tc.range.x + base + threadIdx.x];
-            const float4* r = p.rec + kRecF4 * (int64_t)id;
-            float4 ra = r[0], rb = r[1];
-            float4 rc = r[2];
-            if constexpr (DEPTH) rc.y = 1.f / rc.y;  // depth -> inverse depth
-            scale_entry(ra, rb);
-            s_a[threadIdx.x] = ra;
-            s_b[threadIdx.x] = rb;
-            s_c[threadIdx.x] = rc;
+            Staged e(p, tc, base);
+            act = e.act;
+            if constexpr (DEPTH) e.rc.y = 1.f / e.rc.y;  // depth -> inverse depth
+            s_a[threadIdx.x] = e.ra;
+            s_b[threadIdx.x] = e.rb;
+            s_c[threadIdx.x] = e.rc;
         }
         s_actb[threadIdx.x] = (uint8_t)act;
         __syncthreads();
-        // The two lists of this wave (as render_bwd_kernel): group g's takers among the staged entries (bit 2g + wave of the
-        // activity bytes), back to front, then sentinels up to the longer list's length.  The two 32-lane groups walk their
-        // lists in lock step, each reading its OWN entry: one trip serves up to two different entries, and an entry is
-        // visited only by the blocks that took it.  Wave-private LDS rows: no barrier needed.  The loop is uniform over the
-        // wave (exec stays full: the DPP steps read every lane).
-        int maxn = 0;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const uint32_t gbit = 1u << act_plane(g, wave);
-            uint16_t* lst = s_list[wave][g];
-            int n_g = 0;
-#pragma unroll
-            for (int k = KB / 64 - 1; k >= 0; --k) {   // upper half of the batch first: it is deeper
-                const uint64_t m = __ballot((s_actb[k * 64 + lane] & gbit) != 0);
-                const int c = __popcll(m);
-                if ((m >> lane) & 1ull) lst[n_g + c - 1 - mask_prefix(m)] = (uint16_t)(k * 64 + lane);
-                n_g += c;
-            }
-#pragma unroll
-            for (int t = lane; t < kListLen; t += 64)
-                if (t >= n_g) lst[t] = (uint16_t)KB;
-            maxn = max(maxn, n_g);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        // back to front over the entries this wave's blocks took (hs_replay.h: the back-to-front walk)
+        const int trips = take_lists<KB>(tc, s_actb, s_list);
+        const uint16_t* const my_list = s_list[tc.wave][tc.grp];
 #pragma unroll 1
-        for (int ti = 0; ti < maxn; ++ti) {
-            const int j = (int)my_list[ti];            // (two addresses per wave: one per group)
-            const float4 a = s_a[j];
-            const float4 b = s_b[j];
-            const float4 c = s_c[j];
-            // ---- the forward's alpha: same expressions, same operand order ----
-            const float dx = a.x - tc.pxf;
-            const f2 dy = a.y - tc.pyf;
-            const float t = a.z * dx * dx, u = a.w * dx;
-            const f2 pw = dy * (b.x * dy + u) + t;
-            const f2 G = {hs_exp2(pw.x), hs_exp2(pw.y)};
-            const f2 alpha = {fminf(kAlphaMax, b.y * G.x), fminf(kAlphaMax, b.y * G.y)};
-            // (the sentinel passes the index test for pixels that reach past the batch: its opacity 0 is what keeps it out)
-            const uint32_t idx = (uint32_t)(base + j);
-            const bool act0 = idx < last0 && pw.x <= 0.f && alpha.x >= kAlphaMin;
-            const bool act1 = idx < last1 && pw.y <= 0.f && alpha.y >= kAlphaMin;
+        for (int ti = 0; ti < trips; ++ti) {
+            const BackEntry e = back_entry(tc, s_a, s_b, (int)my_list[ti], base, last0, last1);
+            const float4 a = e.a, b = e.b, c = s_c[e.j];
             // ---- the backward's step (render.hip, step_bwd_pair): inactive pixels keep their state exactly ----
-            const f2 ae = {act0 ? alpha.x : 0.f, act1 ? alpha.y : 0.f};
-            const f2 one_m = splat(1.f) - ae;
-            const f2 rcp = {__builtin_amdgcn_rcpf(one_m.x), __builtin_amdgcn_rcpf(one_m.y)};
-            T *= rcp;  // T_i = T_{i+1} / (1 - alpha_i)
+            const BackStep st = e.step(T);
+            T = st.T;
             f2 cd = (splat(b.z) * dL0 + splat(b.w) * dL1) + splat(c.x) * dL2;  // c_i . dL
             if constexpr (DEPTH) cd += splat(c.y) * dLd;
             const f2 diff = cd - q;
-            const f2 gd = G * (diff * T);
-            q += ae * diff;
-            const f2 dop = {act0 ? gd.x : 0.f, act1 ? gd.y : 0.f};  // select AFTER the product (G may be inf at a skipped pixel)
+            const f2 gd = e.G * (diff * T);
+            q += st.ae * diff;
+            const f2 dop = {e.act0 ? gd.x : 0.f, e.act1 ? gd.y : 0.f};  // select AFTER the product (G may be inf at a skipped pixel)
             const f2 sw = splat(b.y) * dop;
             // ---- the pixel's terms, in the staged conic's units: 2 A2 dx + B2 dy and 2 C2 dy + B2 dx ----
-            const f2 vx = splat(2.f * a.z * dx) + splat(a.w) * dy;
-            const f2 vy = splat(2.f * b.x) * dy + splat(u);
+            const f2 vx = splat(2.f * a.z * e.dx) + splat(a.w) * e.dy;
+            const f2 vy = splat(2.f * b.x) * e.dy + splat(e.u);
             const f2 mx = vx * sw, my = vy * sw;
-            float ax = (act0 ? fabsf(mx.x) : 0.f) + (act1 ? fabsf(mx.y) : 0.f);
-            float ay = (act0 ? fabsf(my.x) : 0.f) + (act1 ? fabsf(my.y) : 0.f);
+            float ax = (e.act0 ? fabsf(mx.x) : 0.f) + (e.act1 ? fabsf(mx.y) : 0.f);
+            float ay = (e.act0 ? fabsf(my.x) : 0.f) + (e.act1 ? fabsf(my.y) : 0.f);
             ax = group_sum(ax);
             ay = group_sum(ay);
             // did a pixel of this lane group composite the entry?  (the forward's activity bit also covers the entry that
             // terminated a pixel, which is not composited)
-            const uint64_t anym = __ballot(act0 || act1);
+            const uint64_t anym = __ballot(e.act0 || e.act1);
             const bool any = (uint32_t)(anym >> (32 * tc.grp)) != 0u;
             // one lane per group, a plain LDS store into the group's own plane of its own entry (the sentinel's is scratch)
-            if ((lane & 31) == 31) s_part[j][plane] = any ? make_float2(ax, ay) : empty_record();
+            if ((lane & 31) == 31) s_part[e.j][plane] = any ? make_float2(ax, ay) : empty_record();
         }
         __syncthreads();
         if ((int)threadIdx.x < cnt) {
-            // the planes the entry's takers wrote (its activity bits), added in plane order
-            AbsAcc o;
-#pragma unroll
-            for (int pl = 0; pl < 4; ++pl)
-                if ((act >> pl) & 1u) o.take(s_part[threadIdx.x][pl]);
+            AbsAcc o = planes_combined<AbsAcc>(act, s_part[threadIdx.x]);
             o.sx *= kx; o.sy *= ky;
             const float4 a = s_a[threadIdx.x], c = s_c[threadIdx.x];
             const int64_t slot = pair_slot(p, a.x, a.y, __float_as_int(c.z), __float_as_uint(c.w), tc.tx, tc.ty);

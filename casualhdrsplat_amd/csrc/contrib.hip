@@ -18,9 +18,10 @@
 // A binning overflow (hs_counters.overflow != 0) is seen ON THE DEVICE: the fold then writes nothing.
 //
 // This unit is compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS), so that the threshold tests below
-// see the bits the forward's saw; the expressions are the forward's, operand for operand.  The forward's decisions a replay
-// repeats (pixel mapping, XCD strip map, staged conic, thresholds, pair_act bits, walk bound, pair slots), the tile context,
-// the segmented sum and the workspace layout are hs_replay.h's, shared with absgrad.hip.
+// see the bits the forward's saw.  The forward's decisions a replay repeats (pixel mapping, XCD strip map, staged conic, alpha
+// and thresholds, pair_act bits, walk bound, pair slots), the staging of an entry, the front-to-back walk (walk_front), the
+// combination of the planes, the tile context, the segmented sum and the workspace layout are hs_replay.h's; this unit keeps
+// what it alone computes from an entry's blending weights.
 #include "hs_replay.h"
 
 namespace hs {
@@ -99,63 +100,32 @@ __global__ void __launch_bounds__(kCBatch) contrib_replay_kernel(Replay p) {
     const int n_proc = walk_bound(s_max, tc);
 
     f2 T = {1.f, 1.f};
-    const uint32_t gbit = 1u << plane;
-    const uint32_t wbits = wave_act_bits(tc.wave);
 
     for (int base = 0; base < n_proc; base += KB) {
         const int cnt = min(KB, n_proc - base);
         __syncthreads();   // the previous batch's write-out has read its records
         uint32_t act = 0;
         if ((int)threadIdx.x < cnt) {
-            const uint32_t id = min(p.point_list[tc.range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
-            act = p.pair_act[(int64_t)tc.range.x + base + threadIdx.x];
-            const float4* r = p.rec + kRecF4 * (int64_t)id;
-            float4 ra = r[0], rb = r[1];
-            const float4 rc = r[2];
-            scale_entry(ra, rb);
-            s_a[threadIdx.x] = ra;
-            s_b[threadIdx.x] = make_float4(rb.x, rb.y, rc.z, rc.w);
+            const Staged e(p, tc, base);
+            act = e.act;
+            s_a[threadIdx.x] = e.ra;
+            s_b[threadIdx.x] = make_float4(e.rb.x, e.rb.y, e.rc.z, e.rc.w);
         }
         s_actb[threadIdx.x] = (uint8_t)act;
         __syncthreads();
-        // every entry one of this wave's two blocks took, front to back; the loop is uniform over the wave (exec stays full:
-        // the DPP steps read every lane)
-#pragma unroll 1
-        for (int k = 0; k < KB / 64; ++k) {
-            uint64_t m = __ballot((s_actb[k * 64 + lane] & wbits) != 0);
-            while (m) {
-                const int j = k * 64 + __builtin_ctzll(m);
-                m &= m - 1;
-                const float4 a = s_a[j];
-                const float4 b = s_b[j];
-                const bool on = (s_actb[j] & gbit) != 0;   // this lane's block took the entry (the forward evaluated it there)
-                // ---- the forward's alpha and the three tests of blend_fwd_pair (hs_replay.h) ----
-                const PairAlpha al = pair_alpha(tc, a, b);
-                const uint32_t idx = (uint32_t)(base + j);
-                const bool act0 = composited(on, idx, last0, al.pw.x, al.al0);
-                const bool act1 = composited(on, idx, last1, al.pw.y, al.al1);
-                const f2 alpha = {al.al0, al.al1};
-                const f2 one = {1.f, 1.f};
-                const f2 test_T = T * (one - alpha);
-                const f2 aT = alpha * T;
-                T = f2{act0 ? test_T.x : T.x, act1 ? test_T.y : T.y};
-                const float v0 = e0 * aT.x, v1 = e1 * aT.y;
-                float sum = (act0 ? v0 : 0.f) + (act1 ? v1 : 0.f);
-                float mx = fmaxf(act0 ? v0 : -INFINITY, act1 ? v1 : -INFINITY);
-                uint32_t c = (act0 && v0 > 0.f ? 1u : 0u) + (act1 && v1 > 0.f ? 1u : 0u);
-                sum = group_sum(sum);
-                mx = group_max(mx);
-                c = group_add_u32(c);
-                if ((lane & 31) == 31 && on) s_part[j][plane] = make_float4(sum, mx, __uint_as_float(c), 0.f);
-            }
-        }
+        walk_front<KB>(tc, s_a, s_b, s_actb, base, last0, last1, T, [&](int j, bool on, bool act0, bool act1, f2 w) {
+            const float v0 = e0 * w.x, v1 = e1 * w.y;
+            float sum = (act0 ? v0 : 0.f) + (act1 ? v1 : 0.f);
+            float mx = fmaxf(act0 ? v0 : -INFINITY, act1 ? v1 : -INFINITY);
+            uint32_t c = (act0 && v0 > 0.f ? 1u : 0u) + (act1 && v1 > 0.f ? 1u : 0u);
+            sum = group_sum(sum);
+            mx = group_max(mx);
+            c = group_add_u32(c);
+            if ((lane & 31) == 31 && on) s_part[j][plane] = make_float4(sum, mx, __uint_as_float(c), 0.f);
+        });
         __syncthreads();
         if ((int)threadIdx.x < cnt) {
-            // the planes the entry's takers wrote (its activity bits), combined in plane order
-            WeightAcc o;
-#pragma unroll
-            for (int pl = 0; pl < 4; ++pl)
-                if ((act >> pl) & 1u) o.take(s_part[threadIdx.x][pl]);
+            const WeightAcc o = planes_combined<WeightAcc>(act, s_part[threadIdx.x]);
             const float4 a = s_a[threadIdx.x], b = s_b[threadIdx.x];
             const int64_t slot = pair_slot(p, a.x, a.y, __float_as_int(b.z), __float_as_uint(b.w), tc.tx, tc.ty);
             if (slot >= 0 && slot < p.capacity) p.pair_rec[slot] = o.row();

@@ -31,7 +31,8 @@
 //                              the mean through z), dL_dopacities, dL_dscales, dL_drotations, every element written.
 // No atomics anywhere: the same inputs give the same bits.  The forward's three workspaces are only read.
 //
-// Compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS); the forward's decisions are hs_replay.h's.
+// Compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS); the forward's decisions, the staging of an entry,
+// both walks, the six geometry sums and the pair record's arithmetic are hs_replay.h's.
 #include "hs_replay.h"
 
 namespace hs {
@@ -42,17 +43,10 @@ constexpr int kDFwdBatch = 128;      // staged entries per batch of the forward 
 constexpr int kDBwdBatch = 64;       // ... of the backward (featgeo.hip: one ballot per list)
 constexpr int kDistSums = 7;         // reduced values per (tile, entry): featgeo's six and dL/ds
 
-__device__ __forceinline__ f2 splat(float v) { f2 r = {v, v}; return r; }
-// number of set bits of a wave-uniform 64-bit mask below this lane
-__device__ __forceinline__ int mask_prefix(uint64_t m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 // 1 / z of the tile's first entry (0 for an empty list): uniform over the workgroup
 __device__ __forceinline__ float tile_s0(const ReplayFrame& p, const TileCtx& tc) {
     if (tc.n <= 0) return 0.f;
-    const uint32_t id = min(p.point_list[tc.range.x], (uint32_t)(p.I - 1));
-    return 1.f / reinterpret_cast<const float*>(p.rec + kRecF4 * (int64_t)id + 2)[1];
+    return 1.f / reinterpret_cast<const float*>(p.rec + kRecF4 * (int64_t)entry_id(p, tc, 0) + 2)[1];
 }
 
 struct DistFwd : ReplayFrame {
@@ -76,7 +70,6 @@ __global__ void __launch_bounds__(kDThreads) distort_fwd_kernel(DistFwd p) {
     __shared__ uint32_t s_max[2];
 
     const TileCtx tc = tile_context(p);
-    const int lane = tc.lane;
     const int64_t HW = (int64_t)p.H * p.W;
 
     uint32_t last0 = 0, last1 = 0;        // per pixel: the number of its last contributor (the forward stopped it there)
@@ -89,54 +82,29 @@ __global__ void __launch_bounds__(kDThreads) distort_fwd_kernel(DistFwd p) {
     const float s0 = n_proc > 0 ? tile_s0(p, tc) : 0.f;
 
     f2 T = {1.f, 1.f}, A = {0.f, 0.f}, D = {0.f, 0.f}, loss = {0.f, 0.f};
-    const uint32_t gbit = 1u << act_plane(tc.grp, tc.wave);
-    const uint32_t wbits = wave_act_bits(tc.wave);
 
     for (int base = 0; base < n_proc; base += KB) {
         const int cnt = min(KB, n_proc - base);
         __syncthreads();   // the previous batch has been walked
         uint32_t act = 0;
         if ((int)threadIdx.x < cnt) {
-            const uint32_t id = min(p.point_list[tc.range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
-            act = p.pair_act[(int64_t)tc.range.x + base + threadIdx.x];
-            const float4* r = p.rec + kRecF4 * (int64_t)id;
-            float4 ra = r[0], rb = r[1];
-            const float depth = reinterpret_cast<const float*>(r + 2)[1];
-            scale_entry(ra, rb);
-            s_a[threadIdx.x] = ra;
-            s_b[threadIdx.x] = make_float4(rb.x, rb.y, 1.f / depth - s0, 0.f);
+            const Staged e(p, tc, base);
+            act = e.act;
+            s_a[threadIdx.x] = e.ra;
+            s_b[threadIdx.x] = make_float4(e.rb.x, e.rb.y, 1.f / e.rc.y - s0, 0.f);
         }
         s_actb[threadIdx.x] = (uint8_t)act;
         __syncthreads();
-        // every entry one of this wave's two blocks took, front to back (uniform over the wave: LDS reads are broadcasts)
-#pragma unroll 1
-        for (int k = 0; k < KB / 64; ++k) {
-            uint64_t m = __ballot((s_actb[k * 64 + lane] & wbits) != 0);
-            while (m) {
-                const int j = k * 64 + __builtin_ctzll(m);
-                m &= m - 1;
-                const float4 a = s_a[j];
-                const float4 b = s_b[j];
-                const bool on = (s_actb[j] & gbit) != 0;   // this lane's block took the entry
-                const PairAlpha al = pair_alpha(tc, a, b);
-                const uint32_t idx = (uint32_t)(base + j);
-                const bool act0 = composited(on, idx, last0, al.pw.x, al.al0);
-                const bool act1 = composited(on, idx, last1, al.pw.y, al.al1);
-                const f2 alpha = {al.al0, al.al1};
-                const f2 one = {1.f, 1.f};
-                const f2 test_T = T * (one - alpha);
-                const f2 w = alpha * T;
-                const f2 sr = splat(b.z);
-                const f2 term = D - sr * A;                     // D_{i-1} - (s_i - s0) A_{i-1}
-                const f2 nloss = w * term + loss;               // (contracted: packed fmas)
-                const f2 nD = w * sr + D;
-                const f2 nA = A + w;
-                T = f2{act0 ? test_T.x : T.x, act1 ? test_T.y : T.y};
-                loss = f2{act0 ? nloss.x : loss.x, act1 ? nloss.y : loss.y};
-                D = f2{act0 ? nD.x : D.x, act1 ? nD.y : D.y};
-                A = f2{act0 ? nA.x : A.x, act1 ? nA.y : A.y};
-            }
-        }
+        walk_front<KB>(tc, s_a, s_b, s_actb, base, last0, last1, T, [&](int j, bool, bool act0, bool act1, f2 w) {
+            const f2 sr = splat(s_b[j].z);
+            const f2 term = D - sr * A;                     // D_{i-1} - (s_i - s0) A_{i-1}
+            const f2 nloss = w * term + loss;               // (contracted: packed fmas)
+            const f2 nD = w * sr + D;
+            const f2 nA = A + w;
+            loss = f2{act0 ? nloss.x : loss.x, act1 ? nloss.y : loss.y};
+            D = f2{act0 ? nD.x : D.x, act1 ? nD.y : D.y};
+            A = f2{act0 ? nA.x : A.x, act1 ? nA.y : A.y};
+        });
     }
     // every in-image pixel of both planes is stored, whatever the list held
     const f2 dist = loss + loss;
@@ -161,19 +129,18 @@ struct alignas(16) DistPart { float v[8]; };   // (seven used)
 
 __global__ void __launch_bounds__(kDThreads) distort_bwd_replay_kernel(DistBwd p) {
     constexpr int KB = kDBwdBatch;
-    constexpr int kListLen = KB + 8;
-    // (record KB of the staging arrays: the sentinel, opacity 0 -- nobody composites it; it pads the shorter list of a wave)
+    // (record KB of the staging arrays: the back-to-front walk's sentinel)
     __shared__ float4 s_a[KB + 1];              // {x, y, A2, B2}
     __shared__ float4 s_b[KB + 1];              // {C2, opacity, radius (int bits), slot start (uint bits)}
     __shared__ float s_s[KB + 1];               // s - s0
     __shared__ DistPart s_part[KB + 1][4];      // plane 2g + w: the totals of lane group g of wave w, stored by that group alone
     __shared__ uint8_t s_actb[kDThreads];       // activity byte of each staged entry (bit 2g + w)
-    __shared__ uint16_t s_list[2][2][kListLen]; // [wave][lane group]: the group's takers among the staged entries, back to front
+    __shared__ uint16_t s_list[2][2][KB + 8];   // [wave][lane group]: the group's takers among the staged entries, back to front
     __shared__ uint32_t s_max[2];
 
     if (p.counters->overflow) return;     // (ReplayFrame: the segmented sum reads no record and no flag of an overflowed frame)
     const TileCtx tc = tile_context(p);
-    const int wave = tc.wave, lane = tc.lane, plane = act_plane(tc.grp, tc.wave);
+    const int lane = tc.lane, plane = act_plane(tc.grp, tc.wave);
     const float s0 = tile_s0(p, tc);
 
     // per pixel: the forward's final transmittance and last contributor, twice the upstream gradient, the totals
@@ -204,7 +171,6 @@ __global__ void __launch_bounds__(kDThreads) distort_bwd_replay_kernel(DistBwd p
     __syncthreads();
     const int n_proc = walk_bound(s_max, tc);
 
-    const uint16_t* const my_list = s_list[wave][tc.grp];
     const int nb = (n_proc + KB - 1) / KB;
     for (int bi = nb - 1; bi >= 0; --bi) {
         const int base = bi * KB;
@@ -212,64 +178,25 @@ __global__ void __launch_bounds__(kDThreads) distort_bwd_replay_kernel(DistBwd p
         __syncthreads();   // the previous batch's write-out has read its records
         uint32_t act = 0;
         if ((int)threadIdx.x < cnt) {
-            const uint32_t id = min(p.point_list[tc.range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
-            act = p.pair_act[(int64_t)tc.range.x + base + threadIdx.x];
-            const float4* r = p.rec + kRecF4 * (int64_t)id;
-            float4 ra = r[0], rb = r[1];
-            const float4 rc = r[2];
-            scale_entry(ra, rb);
-            s_a[threadIdx.x] = ra;
-            s_b[threadIdx.x] = make_float4(rb.x, rb.y, rc.z, rc.w);
-            s_s[threadIdx.x] = 1.f / rc.y - s0;
+            const Staged e(p, tc, base);
+            act = e.act;
+            s_a[threadIdx.x] = e.ra;
+            s_b[threadIdx.x] = make_float4(e.rb.x, e.rb.y, e.rc.z, e.rc.w);
+            s_s[threadIdx.x] = 1.f / e.rc.y - s0;
         }
         s_actb[threadIdx.x] = (uint8_t)act;
         __syncthreads();
-        // The two lists of this wave (as featgeo_replay_kernel): group g's takers among the staged entries, back to front,
-        // then sentinels up to the longer list's length.  Wave-private LDS rows: no barrier needed.  The loop is uniform
-        // over the wave (exec stays full: the DPP steps read every lane).
-        int maxn = 0;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const uint32_t gbit = 1u << act_plane(g, wave);
-            uint16_t* lst = s_list[wave][g];
-            int n_g = 0;
-#pragma unroll
-            for (int k = KB / 64 - 1; k >= 0; --k) {   // upper half of the batch first: it is deeper
-                const uint64_t m = __ballot((s_actb[k * 64 + lane] & gbit) != 0);
-                const int c = __popcll(m);
-                if ((m >> lane) & 1ull) lst[n_g + c - 1 - mask_prefix(m)] = (uint16_t)(k * 64 + lane);
-                n_g += c;
-            }
-#pragma unroll
-            for (int t = lane; t < kListLen; t += 64)
-                if (t >= n_g) lst[t] = (uint16_t)KB;
-            maxn = max(maxn, n_g);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        // back to front over the entries this wave's blocks took (hs_replay.h: the back-to-front walk)
+        const int trips = take_lists<KB>(tc, s_actb, s_list);
+        const uint16_t* const my_list = s_list[tc.wave][tc.grp];
 #pragma unroll 1
-        for (int ti = 0; ti < maxn; ++ti) {
-            const int j = (int)my_list[ti];            // (two addresses per wave: one per group)
-            const float4 a = s_a[j];
-            const float4 b = s_b[j];
-            const f2 sr = splat(s_s[j]);
-            // ---- the forward's alpha: same expressions, same operand order ----
-            const float dx = a.x - tc.pxf;
-            const f2 dy = a.y - tc.pyf;
-            const float t = a.z * dx * dx, u = a.w * dx;
-            const f2 pw = dy * (b.x * dy + u) + t;
-            const f2 G = {hs_exp2(pw.x), hs_exp2(pw.y)};
-            const f2 alpha = {fminf(kAlphaMax, b.y * G.x), fminf(kAlphaMax, b.y * G.y)};
-            // (the sentinel passes the index test for pixels that reach past the batch: its opacity 0 is what keeps it out)
-            const uint32_t idx = (uint32_t)(base + j);
-            const bool act0 = idx < last0 && pw.x <= 0.f && alpha.x >= kAlphaMin;
-            const bool act1 = idx < last1 && pw.y <= 0.f && alpha.y >= kAlphaMin;
+        for (int ti = 0; ti < trips; ++ti) {
+            const BackEntry e = back_entry(tc, s_a, s_b, (int)my_list[ti], base, last0, last1);
+            const f2 sr = splat(s_s[e.j]);
             // ---- the backward's step (render.hip, step_bwd_pair): inactive pixels keep their state exactly ----
-            const f2 ae = {act0 ? alpha.x : 0.f, act1 ? alpha.y : 0.f};
-            const f2 one_m = splat(1.f) - ae;
-            const f2 rcp = {__builtin_amdgcn_rcpf(one_m.x), __builtin_amdgcn_rcpf(one_m.y)};
-            T *= rcp;  // T_i = T_{i+1} / (1 - alpha_i)
-            const f2 w = ae * T;                                 // (0 where the pixel does not composite the entry)
+            const BackStep st = e.step(T);
+            T = st.T;
+            const f2 w = st.ae * T;                              // (0 where the pixel does not composite the entry)
             // ---- d_i = gamma v_i: the total about s_i, and twice the part behind the entry ----
             const f2 suf = sr * Ap - Dp;                         // sum over j > i of w_j (s_i - s_j)
             const f2 tot = M0 - sr * An;                         // sum over all j of w_j (s_j - s_i)
@@ -279,25 +206,16 @@ __global__ void __launch_bounds__(kDThreads) distort_bwd_replay_kernel(DistBwd p
             Ap += w;
             Dp += w * sr;
             const f2 diff = cd - q;
-            const f2 gd = G * (diff * T);
-            q += ae * diff;
-            const f2 dop = {act0 ? gd.x : 0.f, act1 ? gd.y : 0.f};  // select AFTER the product (G may be inf at a skipped pixel)
-            const f2 sw = splat(b.y) * dop;
-            // ---- in-lane sums over the pixel pair (render_bwd_kernel: dx is shared), then the block's 64 pixels ----
-            const f2 m = sw * dy;
-            const f2 m2 = m * dy;
+            const f2 gd = e.G * (diff * T);
+            q += st.ae * diff;
+            const f2 dop = {e.act0 ? gd.x : 0.f, e.act1 ? gd.y : 0.f};  // select AFTER the product (G may be inf at a skipped pixel)
+            const f2 sw = splat(e.b.y) * dop;
             DistPart tot7;
-            const float g0 = (sw.x + sw.y) * dx, g1 = m.x + m.y;
-            tot7.v[0] = group_sum(g0);
-            tot7.v[1] = group_sum(g1);
-            tot7.v[2] = group_sum(g0 * dx);
-            tot7.v[3] = group_sum(g1 * dx);
-            tot7.v[4] = group_sum(m2.x + m2.y);
-            tot7.v[5] = group_sum(dop.x + dop.y);
+            geo_sums(tot7, e, sw, dop);
             tot7.v[6] = group_sum(ds.x + ds.y);                  // (w = 0 where not composited: ds is 0 there)
             tot7.v[7] = 0.f;
             // one lane per group, a plain LDS store into the group's own plane of its own entry (the sentinel's is scratch)
-            if ((lane & 31) == 31) s_part[j][plane] = tot7;
+            if ((lane & 31) == 31) s_part[e.j][plane] = tot7;
         }
         __syncthreads();
         if ((int)threadIdx.x < cnt) {
@@ -306,27 +224,10 @@ __global__ void __launch_bounds__(kDThreads) distort_bwd_replay_kernel(DistBwd p
             if (slot >= 0 && slot < p.capacity) {
                 p.pair_flags[slot] = act != 0 ? 1 : 0;
                 if (act != 0) {
-                    // the planes the entry's takers wrote (its activity bits), added in plane order
-                    float v[kDistSums] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int pl = 0; pl < 4; ++pl) {
-                        if ((act >> pl) & 1u) {
-                            const DistPart s = s_part[threadIdx.x][pl];
-#pragma unroll
-                            for (int k = 0; k < kDistSums; ++k) v[k] += s.v[k];
-                        }
-                    }
-                    // un-scale the conic: A = A2 * (-2/L), B = B2 * (-1/L), C = C2 * (-2/L)  (render_bwd_kernel's write-out)
-                    const float A = a.z * (-2.f / kLog2e), B = a.w * (-1.f / kLog2e), Cc = b.x * (-2.f / kLog2e);
-                    const float ddelx_dx = 0.5f * (float)p.W, ddely_dy = 0.5f * (float)p.H;
-                    // dL/dmean2D = -(A S1 + B S2, C S2 + B S1) (NDC-scaled); dL/dconic = (-0.5 S3, -S4, -0.5 S5)
-                    const float gmx = -(A * v[0] + B * v[1]) * ddelx_dx;
-                    const float gmy = -(Cc * v[1] + B * v[0]) * ddely_dy;
+                    const GeoAcc<kDistSums> sums = planes_combined<GeoAcc<kDistSums>>(act, s_part[threadIdx.x]);
                     float4* o = p.pair_rec + kPairF4 * slot;
-                    o[0] = make_float4(gmx, gmy, -0.5f * v[2], -v[3]);
-                    o[1] = make_float4(-0.5f * v[4], v[5], 0.f, 0.f);     // (no colour gradient: the slots of r, g ...
-                    o[2] = make_float4(0.f, v[6], 0.f, 0.f);              // ... and b stay zero; the inverse depth's is filled)
-                    if constexpr (kPairF4 == 4) o[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+                    write_geo_record(o, geo_record(p, a, b.x, sums.v));
+                    write_geo_record_tail(o, sums.v[6]);   // (the inverse depth's slot is filled)
                 }
             }
         }

@@ -26,7 +26,8 @@
 // the rasterizer's own backward may run before or after this call on the same state.  Every word read from the call's
 // workspace is one the call wrote.  An overflowed frame: the replay returns at once, the segmented sum writes zero rows.
 //
-// Compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS); the forward's decisions are hs_replay.h's.
+// Compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS); the forward's decisions, the staging of an entry and
+// of its feature row, the back-to-front walk, the six geometry sums and the pair record's arithmetic are hs_replay.h's.
 #include "hs_replay.h"
 
 // A/B switch of scripts/time_features_geometry.py (make variant TUS=featgeo DEFS=...).  0, what ships: chosen per pass.
@@ -56,12 +57,6 @@ static_assert(kGeoForce == 0 || kGeoForce == 4 || kGeoForce == 8 || kGeoForce ==
 
 static inline int geo_pass(int left) { return kGeoForce ? kGeoForce : left > 8 ? kGeoPass : left > 4 ? 8 : 4; }
 
-__device__ __forceinline__ f2 splat(float v) { f2 r = {v, v}; return r; }
-// number of set bits of a wave-uniform 64-bit mask below this lane
-__device__ __forceinline__ int mask_prefix(uint64_t m) {
-    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
 struct GeoReplay : ReplayFrame {
     int C, c0, P;                     // channels; the pass's first; Gaussians
     bool vec4;                        // C % 4 == 0 and a 16-byte aligned base: feature rows are read as float4
@@ -77,20 +72,18 @@ struct alignas(8) GeoPart { float v[kGeoSums]; };
 template <int K>
 __global__ void __launch_bounds__(kGThreads) featgeo_replay_kernel(GeoReplay p) {
     constexpr int KB = kGBatch;
-    constexpr int kListLen = KB + 8;
-    // (record KB of the staging arrays: the sentinel, opacity 0 and features 0 -- nobody composites it; it pads the shorter
-    // list of a wave)
+    // (record KB of the staging arrays: the back-to-front walk's sentinel, features 0)
     __shared__ float4 s_a[KB + 1];              // {x, y, A2, B2}
     __shared__ float4 s_b[KB + 1];              // {C2, opacity, radius (int bits), slot start (uint bits)}
     __shared__ alignas(16) float s_f[KB + 1][K];   // the pass's feature values of each staged entry
     __shared__ GeoPart s_part[KB + 1][4];       // plane 2g + w: the totals of lane group g of wave w, stored by that group alone
     __shared__ uint8_t s_actb[kGThreads];       // activity byte of each staged entry (bit 2g + w)
-    __shared__ uint16_t s_list[2][2][kListLen]; // [wave][lane group]: the group's takers among the staged entries, back to front
+    __shared__ uint16_t s_list[2][2][KB + 8];   // [wave][lane group]: the group's takers among the staged entries, back to front
     __shared__ uint32_t s_max[2];
 
     if (p.counters->overflow) return;     // (ReplayFrame: the segmented sum reads no record and no flag of an overflowed frame)
     const TileCtx tc = tile_context(p);
-    const int wave = tc.wave, lane = tc.lane, plane = act_plane(tc.grp, tc.wave);
+    const int lane = tc.lane, plane = act_plane(tc.grp, tc.wave);
     const bool first = p.c0 == 0;         // the pass that writes the records and the flags
 
     // per pixel: the forward's final transmittance and last contributor, the pass's channels of the upstream gradient (0 past
@@ -124,7 +117,6 @@ __global__ void __launch_bounds__(kGThreads) featgeo_replay_kernel(GeoReplay p) 
     __syncthreads();
     const int n_proc = walk_bound(s_max, tc);
 
-    const uint16_t* const my_list = s_list[wave][tc.grp];
     const int nb = (n_proc + KB - 1) / KB;
     for (int bi = nb - 1; bi >= 0; --bi) {
         const int base = bi * KB;
@@ -132,103 +124,42 @@ __global__ void __launch_bounds__(kGThreads) featgeo_replay_kernel(GeoReplay p) 
         __syncthreads();   // the previous batch's write-out has read its records
         uint32_t act = 0;
         if ((int)threadIdx.x < cnt) {
-            const uint32_t id = min(p.point_list[tc.range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
-            act = p.pair_act[(int64_t)tc.range.x + base + threadIdx.x];
-            const float4* r = p.rec + kRecF4 * (int64_t)id;
-            float4 ra = r[0], rb = r[1];
-            const float4 rc = r[2];
-            scale_entry(ra, rb);
-            s_a[threadIdx.x] = ra;
-            s_b[threadIdx.x] = make_float4(rb.x, rb.y, rc.z, rc.w);
-            // the Gaussian of the instance: instance - pose * P (inside [0, P) for every list hs_forward left)
-            const int g = min(max((int)((int64_t)id - (int64_t)tc.pose * p.P), 0), p.P - 1);
-            const float* row = p.features + (int64_t)g * p.C + p.c0;
-            if (p.vec4) {
-#pragma unroll
-                for (int c4 = 0; c4 < K / 4; ++c4) {
-                    const float4 v = p.c0 + 4 * c4 < p.C ? reinterpret_cast<const float4*>(row)[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    reinterpret_cast<float4*>(s_f[threadIdx.x])[c4] = v;
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < K; ++c) s_f[threadIdx.x][c] = p.c0 + c < p.C ? row[c] : 0.f;
-            }
+            const Staged s(p, tc, base);
+            act = s.act;
+            s_a[threadIdx.x] = s.ra;
+            s_b[threadIdx.x] = make_float4(s.rb.x, s.rb.y, s.rc.z, s.rc.w);
+            stage_feature_row(s_f[threadIdx.x], p.features, p.P, p.C, p.c0, p.vec4, s.id, tc.pose);
         }
         s_actb[threadIdx.x] = (uint8_t)act;
         __syncthreads();
-        // The two lists of this wave (as render_bwd_kernel and absgrad_replay_kernel): group g's takers among the staged
-        // entries, back to front, then sentinels up to the longer list's length.  The two 32-lane groups walk their lists in
-        // lock step, each reading its OWN entry.  Wave-private LDS rows: no barrier needed.  The loop is uniform over the
-        // wave (exec stays full: the DPP steps read every lane).
-        int maxn = 0;
-#pragma unroll
-        for (int g = 0; g < 2; ++g) {
-            const uint32_t gbit = 1u << act_plane(g, wave);
-            uint16_t* lst = s_list[wave][g];
-            int n_g = 0;
-#pragma unroll
-            for (int k = KB / 64 - 1; k >= 0; --k) {   // upper half of the batch first: it is deeper
-                const uint64_t m = __ballot((s_actb[k * 64 + lane] & gbit) != 0);
-                const int c = __popcll(m);
-                if ((m >> lane) & 1ull) lst[n_g + c - 1 - mask_prefix(m)] = (uint16_t)(k * 64 + lane);
-                n_g += c;
-            }
-#pragma unroll
-            for (int t = lane; t < kListLen; t += 64)
-                if (t >= n_g) lst[t] = (uint16_t)KB;
-            maxn = max(maxn, n_g);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
+        // back to front over the entries this wave's blocks took (hs_replay.h: the back-to-front walk)
+        const int trips = take_lists<KB>(tc, s_actb, s_list);
+        const uint16_t* const my_list = s_list[tc.wave][tc.grp];
 #pragma unroll 1
-        for (int ti = 0; ti < maxn; ++ti) {
-            const int j = (int)my_list[ti];            // (two addresses per wave: one per group)
-            const float4 a = s_a[j];
-            const float4 b = s_b[j];
-            // ---- the forward's alpha: same expressions, same operand order ----
-            const float dx = a.x - tc.pxf;
-            const f2 dy = a.y - tc.pyf;
-            const float t = a.z * dx * dx, u = a.w * dx;
-            const f2 pw = dy * (b.x * dy + u) + t;
-            const f2 G = {hs_exp2(pw.x), hs_exp2(pw.y)};
-            const f2 alpha = {fminf(kAlphaMax, b.y * G.x), fminf(kAlphaMax, b.y * G.y)};
-            // (the sentinel passes the index test for pixels that reach past the batch: its opacity 0 is what keeps it out)
-            const uint32_t idx = (uint32_t)(base + j);
-            const bool act0 = idx < last0 && pw.x <= 0.f && alpha.x >= kAlphaMin;
-            const bool act1 = idx < last1 && pw.y <= 0.f && alpha.y >= kAlphaMin;
+        for (int ti = 0; ti < trips; ++ti) {
+            const BackEntry en = back_entry(tc, s_a, s_b, (int)my_list[ti], base, last0, last1);
             // ---- d_i of the pass: the entry's K feature values against the pixel pair's K gradients ----
             f2 cd = {0.f, 0.f};
 #pragma unroll
             for (int c4 = 0; c4 < K / 4; ++c4) {
-                const float4 f = reinterpret_cast<const float4*>(s_f[j])[c4];
+                const float4 f = reinterpret_cast<const float4*>(s_f[en.j])[c4];
                 cd += splat(f.x) * e[4 * c4 + 0];
                 cd += splat(f.y) * e[4 * c4 + 1];
                 cd += splat(f.z) * e[4 * c4 + 2];
                 cd += splat(f.w) * e[4 * c4 + 3];
             }
             // ---- the backward's step (render.hip, step_bwd_pair): inactive pixels keep their state exactly ----
-            const f2 ae = {act0 ? alpha.x : 0.f, act1 ? alpha.y : 0.f};
-            const f2 one_m = splat(1.f) - ae;
-            const f2 rcp = {__builtin_amdgcn_rcpf(one_m.x), __builtin_amdgcn_rcpf(one_m.y)};
-            T *= rcp;  // T_i = T_{i+1} / (1 - alpha_i)
+            const BackStep st = en.step(T);
+            T = st.T;
             const f2 diff = cd - q;
-            const f2 gd = G * (diff * T);
-            q += ae * diff;
-            const f2 dop = {act0 ? gd.x : 0.f, act1 ? gd.y : 0.f};  // select AFTER the product (G may be inf at a skipped pixel)
-            const f2 sw = splat(b.y) * dop;
-            // ---- in-lane sums over the pixel pair (render_bwd_kernel: dx is shared), then the block's 64 pixels ----
-            const f2 m = sw * dy;
-            const f2 m2 = m * dy;
+            const f2 gd = en.G * (diff * T);
+            q += st.ae * diff;
+            const f2 dop = {en.act0 ? gd.x : 0.f, en.act1 ? gd.y : 0.f};  // select AFTER the product (G may be inf at a skipped pixel)
+            const f2 sw = splat(en.b.y) * dop;
             GeoPart tot;
-            const float g0 = (sw.x + sw.y) * dx, g1 = m.x + m.y;
-            tot.v[0] = group_sum(g0);
-            tot.v[1] = group_sum(g1);
-            tot.v[2] = group_sum(g0 * dx);
-            tot.v[3] = group_sum(g1 * dx);
-            tot.v[4] = group_sum(m2.x + m2.y);
-            tot.v[5] = group_sum(dop.x + dop.y);
+            geo_sums(tot, en, sw, dop);
             // one lane per group, a plain LDS store into the group's own plane of its own entry (the sentinel's is scratch)
-            if ((lane & 31) == 31) s_part[j][plane] = tot;
+            if ((lane & 31) == 31) s_part[en.j][plane] = tot;
         }
         __syncthreads();
         if ((int)threadIdx.x < cnt) {
@@ -237,37 +168,17 @@ __global__ void __launch_bounds__(kGThreads) featgeo_replay_kernel(GeoReplay p) 
             if (slot >= 0 && slot < p.capacity) {
                 if (first) p.pair_flags[slot] = act != 0 ? 1 : 0;
                 if (act != 0) {
-                    // the planes the entry's takers wrote (its activity bits), added in plane order
-                    float v[kGeoSums] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int pl = 0; pl < 4; ++pl) {
-                        if ((act >> pl) & 1u) {
-                            const GeoPart s = s_part[threadIdx.x][pl];
-#pragma unroll
-                            for (int k = 0; k < kGeoSums; ++k) v[k] += s.v[k];
-                        }
-                    }
-                    // un-scale the conic: A = A2 * (-2/L), B = B2 * (-1/L), C = C2 * (-2/L)  (render_bwd_kernel's write-out)
-                    const float A = a.z * (-2.f / kLog2e), B = a.w * (-1.f / kLog2e), Cc = b.x * (-2.f / kLog2e);
-                    const float ddelx_dx = 0.5f * (float)p.W, ddely_dy = 0.5f * (float)p.H;
-                    // dL/dmean2D = -(A S1 + B S2, C S2 + B S1) (NDC-scaled); dL/dconic = (-0.5 S3, -S4, -0.5 S5)
-                    const float gmx = -(A * v[0] + B * v[1]) * ddelx_dx;
-                    const float gmy = -(Cc * v[1] + B * v[0]) * ddely_dy;
-                    float4 r0 = make_float4(gmx, gmy, -0.5f * v[2], -v[3]);
-                    float2 r1 = make_float2(-0.5f * v[4], v[5]);
+                    const GeoAcc<kGeoSums> sums = planes_combined<GeoAcc<kGeoSums>>(act, s_part[threadIdx.x]);
+                    GeoRec r = geo_record(p, a, b.x, sums.v);
                     float4* o = p.pair_rec + kPairF4 * slot;
                     if (!first) {   // this thread's own record of the earlier passes
                         const float4 o0 = o[0];
                         const float2 o1 = reinterpret_cast<const float2*>(o + 1)[0];
-                        r0 = make_float4(o0.x + r0.x, o0.y + r0.y, o0.z + r0.z, o0.w + r0.w);
-                        r1 = make_float2(o1.x + r1.x, o1.y + r1.y);
+                        r.r0 = make_float4(o0.x + r.r0.x, o0.y + r.r0.y, o0.z + r.r0.z, o0.w + r.r0.w);
+                        r.r1 = make_float2(o1.x + r.r1.x, o1.y + r.r1.y);
                     }
-                    o[0] = r0;
-                    o[1] = make_float4(r1.x, r1.y, 0.f, 0.f);      // (no colour gradient: the slots of r, g ...
-                    if (first) {
-                        o[2] = make_float4(0.f, 0.f, 0.f, 0.f);    // ... b and the inverse depth stay zero)
-                        if constexpr (kPairF4 == 4) o[3] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    }
+                    write_geo_record(o, r);
+                    if (first) write_geo_record_tail(o, 0.f);
                 }
             }
         }

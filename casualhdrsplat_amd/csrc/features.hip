@@ -23,7 +23,8 @@
 // The gradient these kernels deliver reaches the features; the gradient to the geometry (means, covariances, opacities)
 // through the channels -- a C-channel generalisation of render_bwd_kernel -- is featgeo.hip's.
 //
-// Compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS); the forward's decisions are hs_replay.h's.
+// Compiled like render.hip (FMA contraction on: the Makefile's FAST_TUS); the forward's decisions, the staging of an entry and
+// of its feature row, the front-to-back walk and the combination of the planes are hs_replay.h's.
 #include "hs_replay.h"
 
 // A/B switches of scripts/time_features.py (make variant TUS=features DEFS=...).  0, what ships: chosen per call from C, as
@@ -100,8 +101,7 @@ __global__ void __launch_bounds__(kFBatch) features_fwd_kernel(FeatFwd p) {
     __shared__ uint32_t s_max[2];
 
     const TileCtx tc = tile_context(p);
-    const int lane = tc.lane;
-    const int c0 = blockIdx.y * G;        // the group's first channel (c0 < C: the grid)
+    const int c0 = blockIdx.y * G;       // the group's first channel (c0 < C: the grid)
     const int64_t HW = (int64_t)p.H * p.W;
 
     uint32_t last0 = 0, last1 = 0;        // per pixel: the number of its last contributor (the forward stopped it there)
@@ -116,65 +116,28 @@ __global__ void __launch_bounds__(kFBatch) features_fwd_kernel(FeatFwd p) {
     f2 acc[G];
 #pragma unroll
     for (int c = 0; c < G; ++c) acc[c] = f2{0.f, 0.f};
-    const uint32_t gbit = 1u << act_plane(tc.grp, tc.wave);
-    const uint32_t wbits = wave_act_bits(tc.wave);
 
     for (int base = 0; base < n_proc; base += KB) {
         const int cnt = min(KB, n_proc - base);
         __syncthreads();   // the previous batch has been walked
         uint32_t act = 0;
         if ((int)threadIdx.x < cnt) {
-            const uint32_t id = min(p.point_list[tc.range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
-            act = p.pair_act[(int64_t)tc.range.x + base + threadIdx.x];
-            const float4* r = p.rec + kRecF4 * (int64_t)id;
-            float4 ra = r[0], rb = r[1];
-            scale_entry(ra, rb);
-            s_a[threadIdx.x] = ra;
-            s_b[threadIdx.x] = make_float2(rb.x, rb.y);
-            // the Gaussian of the instance: instance - pose * P (inside [0, P) for every list hs_forward left)
-            const int g = min(max((int)((int64_t)id - (int64_t)tc.pose * p.P), 0), p.P - 1);
-            const float* row = p.features + (int64_t)g * p.C + c0;
-            if (p.vec4) {
-#pragma unroll
-                for (int q = 0; q < G / 4; ++q) {
-                    const float4 v = c0 + 4 * q < p.C ? reinterpret_cast<const float4*>(row)[q] : make_float4(0.f, 0.f, 0.f, 0.f);
-                    reinterpret_cast<float4*>(s_f[threadIdx.x])[q] = v;
-                }
-            } else {
-#pragma unroll
-                for (int c = 0; c < G; ++c) s_f[threadIdx.x][c] = c0 + c < p.C ? row[c] : 0.f;
-            }
+            const Staged e(p, tc, base);
+            act = e.act;
+            s_a[threadIdx.x] = e.ra;
+            s_b[threadIdx.x] = make_float2(e.rb.x, e.rb.y);
+            stage_feature_row(s_f[threadIdx.x], p.features, p.P, p.C, c0, p.vec4, e.id, tc.pose);
         }
         s_actb[threadIdx.x] = (uint8_t)act;
         __syncthreads();
-        // every entry one of this wave's two blocks took, front to back (uniform over the wave: LDS reads are broadcasts)
-#pragma unroll 1
-        for (int k = 0; k < KB / 64; ++k) {
-            uint64_t m = __ballot((s_actb[k * 64 + lane] & wbits) != 0);
-            while (m) {
-                const int j = k * 64 + __builtin_ctzll(m);
-                m &= m - 1;
-                const float4 a = s_a[j];
-                const float2 b2 = s_b[j];
-                const float4 b = make_float4(b2.x, b2.y, 0.f, 0.f);
-                const bool on = (s_actb[j] & gbit) != 0;   // this lane's block took the entry
-                const PairAlpha al = pair_alpha(tc, a, b);
-                const uint32_t idx = (uint32_t)(base + j);
-                const bool act0 = composited(on, idx, last0, al.pw.x, al.al0);
-                const bool act1 = composited(on, idx, last1, al.pw.y, al.al1);
-                const f2 alpha = {al.al0, al.al1};
-                const f2 one = {1.f, 1.f};
-                const f2 test_T = T * (one - alpha);
-                const f2 w = alpha * T;
-                T = f2{act0 ? test_T.x : T.x, act1 ? test_T.y : T.y};
+        walk_front<KB>(tc, s_a, s_b, s_actb, base, last0, last1, T, [&](int j, bool, bool act0, bool act1, f2 w) {
 #pragma unroll
-                for (int c = 0; c < G; ++c) {
-                    const float f = s_f[j][c];
-                    const f2 next = w * f2{f, f} + acc[c];          // (contracted: one packed fma)
-                    acc[c] = f2{act0 ? next.x : acc[c].x, act1 ? next.y : acc[c].y};
-                }
+            for (int c = 0; c < G; ++c) {
+                const float f = s_f[j][c];
+                const f2 next = w * f2{f, f} + acc[c];          // (contracted: one packed fma)
+                acc[c] = f2{act0 ? next.x : acc[c].x, act1 ? next.y : acc[c].y};
             }
-        }
+        });
     }
     // every in-image pixel of the group's channels is stored, whatever the list held
     float* o = p.out + ((int64_t)tc.pose * p.C + c0) * HW;
@@ -235,62 +198,32 @@ __global__ void __launch_bounds__(kFBatch) features_bwd_replay_kernel(FeatBwd p,
     const int n_proc = walk_bound(s_max, tc);
 
     f2 T = {1.f, 1.f};
-    const uint32_t gbit = 1u << plane;
-    const uint32_t wbits = wave_act_bits(tc.wave);
 
     for (int base = 0; base < n_proc; base += KB) {
         const int cnt = min(KB, n_proc - base);
         __syncthreads();   // the previous batch's write-out has read its records
         uint32_t act = 0;
         if ((int)threadIdx.x < cnt) {
-            const uint32_t id = min(p.point_list[tc.range.x + base + threadIdx.x], (uint32_t)(p.I - 1));
-            act = p.pair_act[(int64_t)tc.range.x + base + threadIdx.x];
-            const float4* r = p.rec + kRecF4 * (int64_t)id;
-            float4 ra = r[0], rb = r[1];
-            const float4 rc = r[2];
-            scale_entry(ra, rb);
-            s_a[threadIdx.x] = ra;
-            s_b[threadIdx.x] = make_float4(rb.x, rb.y, rc.z, rc.w);
+            const Staged s(p, tc, base);
+            act = s.act;
+            s_a[threadIdx.x] = s.ra;
+            s_b[threadIdx.x] = make_float4(s.rb.x, s.rb.y, s.rc.z, s.rc.w);
         }
         s_actb[threadIdx.x] = (uint8_t)act;
         __syncthreads();
-        // every entry one of this wave's two blocks took, front to back; the loop is uniform over the wave (exec stays full:
-        // the DPP steps read every lane)
-#pragma unroll 1
-        for (int k = 0; k < KB / 64; ++k) {
-            uint64_t m = __ballot((s_actb[k * 64 + lane] & wbits) != 0);
-            while (m) {
-                const int j = k * 64 + __builtin_ctzll(m);
-                m &= m - 1;
-                const float4 a = s_a[j];
-                const float4 b = s_b[j];
-                const bool on = (s_actb[j] & gbit) != 0;
-                const PairAlpha al = pair_alpha(tc, a, b);
-                const uint32_t idx = (uint32_t)(base + j);
-                const bool act0 = composited(on, idx, last0, al.pw.x, al.al0);
-                const bool act1 = composited(on, idx, last1, al.pw.y, al.al1);
-                const f2 alpha = {al.al0, al.al1};
-                const f2 one = {1.f, 1.f};
-                const f2 test_T = T * (one - alpha);
-                const f2 w = alpha * T;
-                T = f2{act0 ? test_T.x : T.x, act1 ? test_T.y : T.y};
-                // a pixel that does not composite the entry is selected out: its gradient, finite or not, adds nothing
-                FeatRec tot;
+        walk_front<KB>(tc, s_a, s_b, s_actb, base, last0, last1, T, [&](int j, bool on, bool act0, bool act1, f2 w) {
+            // a pixel that does not composite the entry is selected out: its gradient, finite or not, adds nothing
+            FeatRec tot;
 #pragma unroll
-                for (int q = 0; q < R; ++q) {
-                    const f2 v = w * e[q];
-                    tot.v[q] = group_sum((act0 ? v.x : 0.f) + (act1 ? v.y : 0.f));
-                }
-                if ((lane & 31) == 31 && on) s_part[j][plane] = tot;
+            for (int q = 0; q < R; ++q) {
+                const f2 v = w * e[q];
+                tot.v[q] = group_sum((act0 ? v.x : 0.f) + (act1 ? v.y : 0.f));
             }
-        }
+            if ((lane & 31) == 31 && on) s_part[j][plane] = tot;
+        });
         __syncthreads();
         if ((int)threadIdx.x < cnt) {
-            // the planes the entry's takers wrote (its activity bits), combined in plane order
-            FeatAcc o;
-#pragma unroll
-            for (int pl = 0; pl < 4; ++pl)
-                if ((act >> pl) & 1u) o.take(s_part[threadIdx.x][pl]);
+            const FeatAcc o = planes_combined<FeatAcc>(act, s_part[threadIdx.x]);
             const float4 a = s_a[threadIdx.x], b = s_b[threadIdx.x];
             const int64_t slot = pair_slot(p, a.x, a.y, __float_as_int(b.z), __float_as_uint(b.w), tc.tx, tc.ty);
             if (slot >= 0 && slot < p.capacity) pair_rec[slot] = o.row();
